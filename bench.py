@@ -39,7 +39,15 @@ The reference has no MLP and no synthetic-stream configs, so those records carry
 (same architecture, trained untimed after the throughput steps) and, at N=1, the
 reference suite's same-model comparison in ``reference_suite``.
 
-Usage: python bench.py --gpus N --steps K --warmup W [--config mlp|rf|stream|rf9]
+A plain run does only what the headline figure needs: set-up, the clock settle, ``--warmup`` steps,
+``--steps`` timed steps, the result line.  ``--full`` adds what takes runs of its own: the accuracy
+figures (the MLP trained on the real WISDM table, held-out synthetic windows), the per-phase times of
+the MLP step and, at N=1, the reference suite.  ``--dump-outputs DIR`` writes what the last timed step
+computed (``DIR/<name>.npy``); with the same arguments the inputs and the model state at the first
+warm-up step are the same from run to run.
+
+Usage: python bench.py --gpus N --steps K --warmup W [--config mlp|rf|stream|rf9] [--full]
+                       [--dump-outputs DIR]
 """
 from __future__ import annotations
 
@@ -114,6 +122,49 @@ def settle_clocks(ctx, run, ms, dev):
             return el
 
 
+def settle_engine(ctx, eng, run, args, dev):
+    """``settle_clocks`` for a step that trains ``eng``.  Under ``--dump-outputs`` the engine's state
+    (parameters, Adam moments, step count) is put back afterwards: how many settle steps fit into
+    ``--settle-ms`` depends on the clock, and the dumped state must depend on the arguments alone."""
+    st = None
+    if args.dump_outputs and args.settle_ms > 0 and dev.type == "cuda":
+        st = {k: v.clone() for k, v in eng.state_tensors().items()}
+    ms = settle_clocks(ctx, run, args.settle_ms, dev)
+    if st is not None:
+        eng.load_state(st)
+    return ms
+
+
+def engine_outputs(eng):
+    """What a caller of ``MLPEngine.train_step`` holds after the step: the parameters, the Adam
+    moments and, from the native step, the batch's summed loss and its count of correct rows."""
+    st = eng.state_tensors()
+    out = {"params": st["P"].clone(), "adam_m": st["m"].clone(), "adam_v": st["v"].clone()}
+    if eng.native:
+        out["loss_correct"] = torch.tensor(eng.last_loss_and_correct(), dtype=torch.float64)
+    return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """``--dump-outputs``: every array as ``out_dir/<name>.npy`` (float64 for 64-bit sources, float32
+    otherwise), DUMP_LIMIT_BYTES in all: an array over its share of the limit is stored as a fixed
+    seeded sample of its elements (ascending flat indices, the same for every run of one shape)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    for name, t in arrays.items():
+        t = torch.as_tensor(t).detach().cpu()
+        a = t.to(torch.float64 if t.dtype in (torch.float64, torch.int64) else torch.float32).contiguous().numpy()
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(2018).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def capture_steps(step, nslots, enable):
     """HIP-graph capture of one training step per batch slot (launch-bound inner loop)."""
     if not enable:
@@ -180,26 +231,29 @@ def bench_mlp(args, ctx):
             eng.gather_phase()
     else:
         run = step
-    # the untimed WISDM accuracy run (a separate engine) goes first: the timed steps then start on a
-    # GPU already out of its idle power state instead of ramping its clock inside a 20-step window
-    extras = wisdm_accuracy_fields(args, ctx, hidden=(args.hidden, args.hidden))
-    settle_ms = settle_clocks(ctx, run, args.settle_ms, dev)
+    # --full: the untimed WISDM accuracy run (a separate engine) goes first: the timed steps then start
+    # on a GPU already out of its idle power state instead of ramping its clock inside a 20-step window
+    extras = wisdm_accuracy_fields(args, ctx, hidden=(args.hidden, args.hidden)) if args.full else {}
+    settle_ms = settle_engine(ctx, eng, run, args, dev)
     elapsed = timed(ctx, run, args.steps, args.warmup, dev)
-    # accuracy of the model the timed steps trained, before the phase probe's extra steps move it
-    Xt, yt = synthetic_windows(65536, seed=999, device=dev)
-    acc = float((torch.argmax(eng.logits(Xt), dim=1) == yt).float().mean())
-    phases = mlp_phase_times(ctx, eng, Xin, y32, B, nb, global_batch, n=max(10, min(50, args.steps)))
+    outputs = engine_outputs(eng) if args.dump_outputs else None
+    if args.full:
+        # accuracy of the model the timed steps trained, before the phase probe's extra steps move it
+        Xt, yt = synthetic_windows(65536, seed=999, device=dev)
+        acc = float((torch.argmax(eng.logits(Xt), dim=1) == yt).float().mean())
+        extras["synthetic_test_accuracy"] = hdist.mean_over_ranks(ctx, acc)
+        extras["phase_ms"] = mlp_phase_times(ctx, eng, Xin, y32, B, nb, global_batch, n=max(10, min(50, args.steps)))
     rec = {"value": global_batch * args.steps / elapsed, "ms_per_step": elapsed * 1e3 / args.steps,
+           "outputs": outputs,
            "vs_baseline": None, "vs_baseline_note": BASELINE_NOTE,
            "data": "synthetic WISDM-shaped windows (43 features, 6 classes, class-conditional Gaussian); "
                    "random-init weights",
            "config": {"model": f"WISDM 6-class 3-layer MLP bf16 ({'-'.join(map(str, layers))})",
                       "global_batch": global_batch, "seq_len": None, "features": N_FEATURES,
                       "parallelism": f"dp{world}"},
-           "synthetic_test_accuracy": hdist.mean_over_ranks(ctx, acc),
            "hip_graph": {0: "off", 1: "whole-step", 2: "segmented"}[mode if graphs else 0],
            "collectives_per_step": eng.collective_stats() if hasattr(eng, "collective_stats") else None,
-           "phase_ms": phases, "settle_ms": settle_ms}
+           "settle_ms": settle_ms}
     rec.update(extras)
     return rec
 
@@ -277,6 +331,7 @@ def bench_reference(args, ctx):
     models = r["models"]
     per_step = r["suite_fit_s"]
     return {"value": r["suite_train_windows_per_s"],
+            "outputs": {"accuracy": torch.tensor([models[k]["accuracy"] for k in sorted(models)], dtype=torch.float64)},
             "ms_per_step": per_step * 1e3, "vs_baseline": r["suite_vs_baseline"],
             "unit_note": "4 x N_train windows / (t_LR + t_LR-CV + t_DT + t_RF); median fit time per model",
             "data": f"WISDM v1.1 transformed table (tests/data/wisdm_data.csv), reference encoding "
@@ -313,28 +368,34 @@ def bench_infer(args, ctx):
     nb = 4
     X, y = synthetic_windows(B * nb, seed=500 + rank, device=dev)
     correct = torch.zeros((), dtype=torch.int64, device=dev)
+    last = {}
 
     def step(i):
         j = i % nb
         xb = X[j * B:(j + 1) * B]
         if eng.native:
-            _, pred = eng.infer_fused_f32(xb)  # raw fp32 features in: cast kernel + the step's INFER forward
+            z, pred = eng.infer_fused_f32(xb)  # raw fp32 features in: cast kernel + the step's INFER forward
         else:
-            pred = torch.argmax(eng.logits(xb), 1)
-        if i < nb:
+            z = eng.logits(xb)
+            pred = torch.argmax(z, 1)
+        last["logits"], last["prediction"] = z, pred
+        if args.full and i < nb:
             correct.add_((pred.long() == y[j * B:(j + 1) * B]).sum())
 
     settle_ms = settle_clocks(ctx, step, args.settle_ms, dev)
     elapsed = timed(ctx, step, args.steps, args.warmup, dev)
-    acc = float(correct) / (B * min(nb, args.steps + args.warmup))
+    outputs = {k: v.clone() for k, v in last.items()} if args.dump_outputs else None
+    extras = {}
+    if args.full:
+        acc = float(correct) / (B * min(nb, args.steps + args.warmup))
+        extras = {"test_accuracy": hdist.mean_over_ranks(ctx, acc), "test_accuracy_data": "held-out synthetic windows"}
     return {"value": B * world * args.steps / elapsed, "ms_per_step": elapsed * 1e3 / args.steps,
-            "vs_baseline": None,
+            "vs_baseline": None, "outputs": outputs, **extras,
             "data": "synthetic WISDM-shaped windows (43 features, 6 classes); MLP trained "
                     f"{args.train_steps} steps on synthetic windows first (untimed)",
             "config": {"model": f"WISDM 6-class 3-layer MLP bf16 inference ({'-'.join(map(str, layers))})",
                        "global_batch": B * world, "seq_len": None, "features": N_FEATURES,
                        "parallelism": f"dp{world}"},
-            "test_accuracy": hdist.mean_over_ranks(ctx, acc), "test_accuracy_data": "held-out synthetic windows",
             "mode": "inference", "settle_ms": settle_ms}
 
 
@@ -375,9 +436,6 @@ def bench_rf(args, ctx, nine_axis=False, single_tree=False):
         X, y = _featurized(n_local, spec, dev, first_window=rank * n_local)
     if not nine_axis:
         X = X[:, :N_FEATURES].contiguous()  # the WISDM-43 feature set
-    Xt, yt = _featurized(4096, spec, dev, first_window=10 ** 9)
-    if not nine_axis:
-        Xt = Xt[:, :N_FEATURES].contiguous()
     if single_tree:  # every feature at every node: sibling subtraction applies (--no-subtract: off)
         tree_mod.SIBLING_SUBTRACTION = not args.no_subtract
         tree_mod.SUBTRACT_MIN_PAIRS = 0  # measure the subtraction at every size
@@ -405,7 +463,15 @@ def bench_rf(args, ctx, nine_axis=False, single_tree=False):
         for k in st:
             st[k] = 0
     elapsed = timed(ctx, run, args.steps, args.warmup, dev)
-    acc = float((model["m"].predict(Xt) == yt).float().mean())
+    extras = {}
+    if args.full:
+        Xt, yt = _featurized(4096, spec, dev, first_window=10 ** 9)
+        if not nine_axis:
+            Xt = Xt[:, :N_FEATURES].contiguous()
+        acc = float((model["m"].predict(Xt) == yt).float().mean())
+        extras = {"test_accuracy": hdist.mean_over_ranks(ctx, acc), "test_accuracy_data": "held-out synthetic windows"}
+    # the fitted forest's node arrays (feature, threshold, children, class counts, nodes per tree)
+    outputs = {k: v for k, v in model["m"].state().items() if k != "max_depth"} if args.dump_outputs else None
     rows = n_local * world
     if mode == "tree" and world > 1:
         coll = {k: v / (args.steps + args.warmup) for k, v in tp_stats.items()}
@@ -426,8 +492,7 @@ def bench_rf(args, ctx, nine_axis=False, single_tree=False):
             "data": f"synthetic {spec.axes}-axis {spec.hz:g} Hz streams featurized on device "
                     f"({X.shape[1]} features, {K} classes)",
             "config": {"model": name, "global_batch": rows, "seq_len": spec.window, "parallelism": f"dp{world}"},
-            "test_accuracy": hdist.mean_over_ranks(ctx, acc), "test_accuracy_data": "held-out synthetic windows",
-            "dtype": "fp32", "rf_parallel": mode, "settle_ms": settle_ms,
+            "outputs": outputs, **extras, "dtype": "fp32", "rf_parallel": mode, "settle_ms": settle_ms,
             "histogram_reduction": (args.rf_reduce if mode == "data" else "none (tree parallel)") if world > 1 else "none",
             "collectives_per_step": coll}
 
@@ -527,21 +592,23 @@ def bench_stream(args, ctx):
 
     if args.stream_pass:
         rec = _stream_full_pass(args, ctx, spec, stream, labels, eng, mean, inv_std, samples_local)
-        rec.update(test_accuracy=held_out_accuracy(),
-                   test_accuracy_data="held-out synthetic stream (8192 windows past every shard), after the timed passes")
+        if args.full:
+            rec.update(test_accuracy=held_out_accuracy(), test_accuracy_data="held-out synthetic stream (8192 windows "
+                                                                             "past every shard), after the timed passes")
         return rec
-    settle_ms = settle_clocks(ctx, step, args.settle_ms, dev)
+    settle_ms = settle_engine(ctx, eng, step, args, dev)
     elapsed = timed(ctx, step, args.steps, args.warmup, dev)
-    acc = held_out_accuracy()
+    outputs = engine_outputs(eng) if args.dump_outputs else None
+    extras = {"test_accuracy": held_out_accuracy(), "test_accuracy_data": "held-out synthetic stream"} if args.full else {}
     return {"value": global_batch * args.steps / elapsed, "ms_per_step": elapsed * 1e3 / args.steps,
-            "vs_baseline": None, "vs_baseline_note": BASELINE_NOTE,
+            "vs_baseline": None, "vs_baseline_note": BASELINE_NOTE, "outputs": outputs, **extras,
             "samples_per_s": global_batch * W * args.steps / elapsed,
             "data": f"synthetic 3-axis 20 Hz stream, {samples_local * world / 1e9:.2f}B samples resident "
                     f"({samples_local / 1e6:.0f}M per GPU), featurized + standardized on device each step",
             "config": {"model": f"raw stream -> window features ({F}) -> MLP bf16 "
                                 f"({F}-{args.hidden}-{args.hidden}-{N_CLASSES})",
                        "global_batch": global_batch, "seq_len": W, "parallelism": f"dp{world}"},
-            "test_accuracy": acc, "test_accuracy_data": "held-out synthetic stream", "settle_ms": settle_ms,
+            "settle_ms": settle_ms,
             "stream_overlap": bool(eng.native and args.stream_overlap)}
 
 
@@ -592,11 +659,12 @@ def _stream_full_pass(args, ctx, spec, stream, labels, eng, mean, inv_std, sampl
             nxt = (X[(j + 1) * B:(j + 2) * B], y32[(j + 1) * B:(j + 2) * B]) if j + 1 < nb and eng.native else None
             eng.train_step(X[j * B:(j + 1) * B], y32[j * B:(j + 1) * B], gb, prefetch=nxt)
 
-    settle_ms = settle_clocks(ctx, one_pass, args.settle_ms, dev)
+    settle_ms = settle_engine(ctx, eng, one_pass, args, dev)
     elapsed = timed(ctx, one_pass, args.steps, args.warmup, dev)
     trained = nb * gb
     return {"value": trained * args.steps / elapsed, "ms_per_step": elapsed * 1e3 / args.steps,
             "vs_baseline": None, "vs_baseline_note": BASELINE_NOTE,
+            "outputs": engine_outputs(eng) if args.dump_outputs else None,
             "samples_per_s": samples_local * world * args.steps / elapsed,
             "windows_featurized_per_pass": xin_rows.get("n", 0) * world, "mlp_steps_per_pass": nb,
             "data": f"synthetic 3-axis {spec.hz:g} Hz stream, {samples_local * world / 1e9:.2f}B samples resident "
@@ -641,6 +709,12 @@ def main():
                     help="--config stream: time full passes over every resident sample (halo-sharded featurization "
                          "+ one MLP epoch) instead of per-batch steps")
     ap.add_argument("--out", type=str, default="")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the accuracy figures (WISDM MLP, "
+                         "held-out windows), the MLP step's per-phase times, the reference suite at N=1")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / "
+                         "float64, 64 MB at most; a fixed seeded sample of a larger array); rank 0 writes")
     ap.add_argument("--stream-overlap", type=int, default=int(os.environ.get("HAR_STREAM_OVERLAP", "0")),
                     help="--config stream: featurize batch i+1 on a side stream while batch i trains (1) or "
                          "featurize then train in one stream (0)")
@@ -662,12 +736,15 @@ def main():
         r = bench_reference(args, ctx)
     else:
         r = bench_rf(args, ctx, nine_axis=args.config == "rf9", single_tree=args.config == "dt")
+    outputs = r.pop("outputs", None)
+    if args.dump_outputs and ctx.rank == 0:
+        dump_outputs(args.dump_outputs, outputs)
     rec = {"metric": METRIC, "value": r.pop("value"), "unit": "windows/s", "n_gpus": ctx.world_size,
            "steps": args.steps, "warmup": args.warmup, "ms_per_step": r.pop("ms_per_step"),
            "higher_is_better": True, "scaling": "weak", "vs_baseline": r.pop("vs_baseline"),
            "dtype": r.pop("dtype", "bf16"), "data": r.pop("data"), "config": r.pop("config")}
     rec.update(r)
-    if args.config == "mlp" and ctx.world_size == 1 and not args.no_wisdm:
+    if args.full and args.config == "mlp" and ctx.world_size == 1 and not args.no_wisdm:
         # same-model comparison against the reference's published fits, recorded with the headline run
         from har.suite import run_reference_suite
 

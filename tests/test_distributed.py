@@ -249,7 +249,7 @@ def test_tree_parallel_forest_equals_single(world):
     torch.testing.assert_close(outs[0], single.predict_raw(X))
 
 
-@pytest.mark.parametrize("config,extra", [("mlp", ["--batch", "512"]), ("rf", ["--rows", "3000", "--trees", "3"]),
+@pytest.mark.parametrize("config,extra", [("mlp", ["--batch", "512", "--full"]), ("rf", ["--rows", "3000", "--trees", "3"]),
                                           ("stream", ["--stream-pass", "--samples", "8000000", "--batch", "512"])])
 def test_bench_contract_torchrun(config, extra):
     """The driver's N>1 launch (``torch.distributed.run ... bench.py --gpus N``) on 2 gloo ranks:

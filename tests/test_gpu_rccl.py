@@ -338,7 +338,7 @@ def test_rccl_bench_graph2_subprocess(cuda, tmp_path, graph):
     if graph == "2":
         env["HAR_MLP_SHARDED_OPT"] = "1"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2",
-                        "--graph", graph, "--no-wisdm", "--settle-ms", "0"],
+                        "--graph", graph, "--no-wisdm", "--settle-ms", "0", "--full"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
