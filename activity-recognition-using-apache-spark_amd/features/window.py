@@ -11,6 +11,12 @@ definitions in PyTorch (oracle).
 
 Feature row for A axes (``feature_names``), WISDM-43 first when A = 3:
 ``[A x 10 bins][avg A][peak A][absdev A][std A][resultant A/3][min A][max A][energy A][corr 3 per triad]``.
+
+All of these are time-domain statistics.  The frequency-domain columns (band energies, dominant
+frequency, spectral centroid and entropy: ``features.spectral``, a second HIP kernel that runs the DFT on
+the matrix cores) are opt-in: ``WindowFeaturizer(spectral=True)`` returns ``[time | spectral]`` rows,
+``28 A + 4 (A // 3)`` wide, both kernels writing into one buffer, and ``window_spectral_features_mlp``
+gives the same rows as bf16 training input.
 """
 from __future__ import annotations
 
@@ -19,6 +25,8 @@ from typing import List, Sequence
 import torch
 
 from ..ops import _native
+from .spectral import (n_spectral_features, spectral_feature_names, spectral_features_into, spectral_features_mlp,
+                       spectral_features_torch)
 
 NBINS = 10
 
@@ -112,6 +120,22 @@ def _is_wide(err: RuntimeError) -> bool:
     return "contract violation code -5" in str(err)
 
 
+def _window_features_into(stream: torch.Tensor, window: int, stride: int, hz: float, out: torch.Tensor) -> None:
+    """Device path: the window kernel writes columns ``[0, n_features(A))`` of the fp32 rows ``out``."""
+    S, A = stream.shape
+    nw = window_count(S, window, stride)
+    if not nw:
+        return
+    s = stream.contiguous().float()
+    try:
+        _native.kernels().window_features(s.data_ptr(), S, A, window, stride, nw, float(hz), NBINS,
+                                          out.data_ptr(), out.stride(0), _native.stream_ptr())
+    except RuntimeError as e:
+        if not _is_wide(e):
+            raise
+        out[:, :n_features(A)] = _wide_windows(s, window, stride, hz)
+
+
 def window_features(stream: torch.Tensor, window: int, stride: int, hz: float) -> torch.Tensor:
     """[S, A] raw samples -> [n_windows, n_features(A)] features (GPU kernel on device tensors; windows too
     wide for its LDS images: the torch definition on the device, with a warning)."""
@@ -120,18 +144,25 @@ def window_features(stream: torch.Tensor, window: int, stride: int, hz: float) -
         raise ValueError("axes must be 3, 6 or 9")
     if not stream.is_cuda:
         return window_features_torch(stream, window, stride, hz)
-    nw = window_count(S, window, stride)
+    out = torch.empty(window_count(S, window, stride), n_features(A), dtype=torch.float32, device=stream.device)
+    _window_features_into(stream, window, stride, hz, out)
+    return out
+
+
+def window_spectral_features(stream: torch.Tensor, window: int, stride: int, hz: float) -> torch.Tensor:
+    """[S, A] raw samples -> [n_windows, 28 A + 4 (A // 3)] rows ``[time | spectral]``.  On the device the
+    window kernel and the spectral kernel write their columns of ONE buffer (no concatenation)."""
+    S, A = stream.shape
+    if A % 3 or A > 9:
+        raise ValueError("axes must be 3, 6 or 9")
+    if not stream.is_cuda:
+        return torch.cat([window_features_torch(stream, window, stride, hz),
+                          spectral_features_torch(stream, window, stride, hz)], 1)
     F = n_features(A)
-    out = torch.empty(nw, F, dtype=torch.float32, device=stream.device)
-    if nw:
-        s = stream.contiguous().float()
-        try:
-            _native.kernels().window_features(s.data_ptr(), S, A, window, stride, nw, float(hz), NBINS,
-                                              out.data_ptr(), F, _native.stream_ptr())
-        except RuntimeError as e:
-            if not _is_wide(e):
-                raise
-            return _wide_windows(s, window, stride, hz)
+    out = torch.empty(window_count(S, window, stride), F + n_spectral_features(A), dtype=torch.float32,
+                      device=stream.device)
+    _window_features_into(stream, window, stride, hz, out)
+    spectral_features_into(stream, window, stride, hz, out, F)
     return out
 
 
@@ -169,22 +200,46 @@ def window_features_mlp(stream: torch.Tensor, window: int, stride: int, hz: floa
     return out
 
 
+def window_spectral_features_mlp(stream: torch.Tensor, window: int, stride: int, hz: float, mean: torch.Tensor,
+                                 inv_std: torch.Tensor, in_pad: int, nan_value: float = -1.0,
+                                 out: torch.Tensor = None) -> torch.Tensor:
+    """The ``[time | spectral]`` rows as bf16 training input: ``window_features_mlp`` writes the time
+    columns and the zero padding, then ``spectral_features_mlp`` the ``11 A`` columns after them (3 axes:
+    88 features in a 96-wide row).  ``mean`` / ``inv_std`` hold the statistics of all ``28 A + 4 (A // 3)``
+    columns."""
+    S, A = stream.shape
+    F = n_features(A)
+    Fs = n_spectral_features(A)
+    if in_pad < F + Fs:
+        raise ValueError(f"in_pad {in_pad} is narrower than the {F + Fs} features")
+    if mean.numel() != F + Fs or inv_std.numel() != F + Fs:
+        raise ValueError(f"mean / inv_std must hold the {F + Fs} statistics of the combined row")
+    out = window_features_mlp(stream, window, stride, hz, mean[:F], inv_std[:F], in_pad, nan_value, out)
+    return spectral_features_mlp(stream, window, stride, hz, mean[F:], inv_std[F:], out, F)
+
+
 class WindowFeaturizer:
     """``transform(stream [S, A]) -> features [W, F]`` with the WISDM window defaults
-    (10 s at ``hz``; non-overlapping unless ``overlap`` > 0)."""
+    (10 s at ``hz``; non-overlapping unless ``overlap`` > 0).  ``spectral=True`` appends the spectral
+    columns (``features.spectral``) to the time-domain ones."""
 
     def __init__(self, hz: float = 20.0, seconds: float = 10.0, overlap: float = 0.0,
-                 axis_names: Sequence[str] = ("X", "Y", "Z")):
+                 axis_names: Sequence[str] = ("X", "Y", "Z"), spectral: bool = False):
         self.hz = hz
         self.window = int(round(hz * seconds))
         self.stride = max(1, int(round(self.window * (1.0 - overlap))))
         self.axis_names = list(axis_names)
+        self.spectral = spectral
 
     @property
     def names(self) -> List[str]:
+        if self.spectral:
+            return feature_names(self.axis_names) + spectral_feature_names(self.axis_names)
         return feature_names(self.axis_names)
 
     def transform(self, stream: torch.Tensor) -> torch.Tensor:
+        if self.spectral:
+            return window_spectral_features(stream, self.window, self.stride, self.hz)
         return window_features(stream, self.window, self.stride, self.hz)
 
     def halo(self) -> int:

@@ -659,6 +659,20 @@ PYBIND11_MODULE(_har_native, m) {
                               P<float>(out), ld_out, S(st)),
           "window_features");
   });
+  m.def("spectral_features", [](u stream, int64_t n_samples, int axes, int window, int stride, int64_t n_windows,
+                                float hz, u out, int ld_out, int col0, u st) {
+    check(har_spectral_features(P<const float>(stream), n_samples, axes, window, stride, n_windows, hz, P<float>(out),
+                                ld_out, col0, S(st)),
+          "spectral_features");
+  });
+  m.def("spectral_features_mlp", [](u stream, int64_t n_samples, int axes, int window, int stride, int64_t n_windows,
+                                    float hz, u mean, u inv_std, u out, int ld_out, int col0, u st) {
+    check(har_spectral_features_mlp(P<const float>(stream), n_samples, axes, window, stride, n_windows, hz,
+                                    P<const float>(mean), P<const float>(inv_std), P<uint16_t>(out), ld_out, col0,
+                                    S(st)),
+          "spectral_features_mlp");
+  });
+  m.def("spectral_max_window", []() { return har_spectral_max_window(); });
 
   m.def("grad_reduce_adam", [](std::vector<u> src, std::vector<int64_t> start, std::vector<int64_t> len,
                                std::vector<int64_t> lds, std::vector<int> nsl, int64_t n, u G, u param, u mm, u vv,

@@ -346,6 +346,21 @@ int har_window_features(const float* stream, int64_t n_samples, int axes, int wi
 // Probe switch: 1 = the pre-v3 (per-sample LDS reads) window kernels only, 0 = default selection.
 void har_window_set_legacy(int on);
 
+// ---- spectral window features (spectral.hip): the DFT of every (window, axis) on the matrix cores ----
+// 11 features per axis — 8 band fractions, dominant frequency, centroid, entropy — laid out
+// [A x 8 bands][dominant Hz: A][centroid Hz: A][entropy: A], written as fp32 into columns
+// [col0, col0 + 11 A) of rows [n_windows][ld_out].  Contract codes as har_window_features: -2 bad shape,
+// -3 windows past the stream, -4 null pointer or row too narrow, -5 window longer than
+// har_spectral_max_window() (or a span that does not fit the LDS).
+int har_spectral_features(const float* stream, int64_t n_samples, int axes, int window, int stride,
+                          int64_t n_windows, float hz, float* out, int ld_out, int col0, hipStream_t s);
+// Training-input variant: bf16 ((v - mean[f]) * inv_std[f]), f in [0, 11 A), into columns [col0, col0 + 11 A)
+// of an existing bf16 row buffer (the features are never NaN: no fill value).
+int har_spectral_features_mlp(const float* stream, int64_t n_samples, int axes, int window, int stride,
+                              int64_t n_windows, float hz, const float* mean, const float* inv_std, uint16_t* out,
+                              int ld_out, int col0, hipStream_t s);
+int har_spectral_max_window();
+
 // ---- trees ----
 // Fused per-level histogram + best split; grid (feature chunks, active nodes).
 // rows/row_w list each node's rows contiguously (node_start/node_count); feats [A][m].

@@ -111,6 +111,28 @@ static void window_contracts() {
   EXPECT(har_window_features_mlp(fbuf, 1000, 3, 200, 100, -3, 20.f, fbuf, fbuf, 0.f, hbuf, 64, 0), -2);
   // a window longer than the int32 sample counter range of the kernel
   EXPECT(har_window_features(fbuf, int64_t(1) << 40, 3, 70000, 100, 5, 20.f, 10, fbuf, 64, 0), -2);
+  // spectral features, the same codes: axes, short window, stride, window count, column offset, rate;
+  // windows past the stream; null pointers and rows too narrow for col0 + 11 A; windows over the maximum
+  EXPECT(har_spectral_features(fbuf, 1000, 4, 200, 100, 5, 20.f, fbuf, 64, 0, 0), -2);
+  EXPECT(har_spectral_features(fbuf, 1000, 3, 2, 100, 5, 20.f, fbuf, 64, 0, 0), -2);
+  EXPECT(har_spectral_features(fbuf, 1000, 3, 200, 0, 5, 20.f, fbuf, 64, 0, 0), -2);
+  EXPECT(har_spectral_features(fbuf, 1000, 3, 200, 100, -1, 20.f, fbuf, 64, 0, 0), -2);
+  EXPECT(har_spectral_features(fbuf, 1000, 3, 200, 100, 5, 20.f, fbuf, 64, -1, 0), -2);
+  EXPECT(har_spectral_features(fbuf, 1000, 3, 200, 100, 5, 0.f, fbuf, 64, 0, 0), -2);
+  EXPECT(har_spectral_features(fbuf, 1000, 3, 200, 100, 10, 20.f, fbuf, 64, 0, 0), -3);
+  EXPECT(har_spectral_features(fbuf, 1000, 3, 200, 100, 5, 20.f, fbuf, 32, 0, 0), -4);
+  EXPECT(har_spectral_features(fbuf, 1000, 3, 200, 100, 5, 20.f, fbuf, 64, 32, 0), -4);
+  EXPECT(har_spectral_features(fbuf, 1000, 3, 200, 100, 5, 20.f, nullptr, 64, 0, 0), -4);
+  EXPECT(har_spectral_features(nullptr, 1000, 3, 200, 100, 5, 20.f, fbuf, 64, 0, 0), -4);
+  EXPECT(har_spectral_features(fbuf, 1000, 3, 200, 100, 0, 20.f, fbuf, 64, 0, 0), 0);  // nothing to do
+  EXPECT(har_spectral_features(fbuf, 100000, 3, har_spectral_max_window() + 1, 100, 5, 20.f, fbuf, 64, 0, 0), -5);
+  EXPECT(har_spectral_features(fbuf, 100000, 9, 2600, 1300, 5, 50.f, fbuf, 128, 0, 0), -5);
+  EXPECT(har_spectral_features_mlp(fbuf, 1000, 3, 200, 100, 5, 20.f, nullptr, fbuf, hbuf, 96, 55, 0), -4);
+  EXPECT(har_spectral_features_mlp(fbuf, 1000, 3, 200, 100, 5, 20.f, fbuf, fbuf, hbuf, 64, 55, 0), -4);
+  EXPECT(har_spectral_features_mlp(fbuf, 1000, 3, 200, 100, 10, 20.f, fbuf, fbuf, hbuf, 96, 55, 0), -3);
+  EXPECT(har_spectral_features_mlp(fbuf, 1000, 6, 200, 100, -3, 20.f, fbuf, fbuf, hbuf, 192, 110, 0), -2);
+  EXPECT(har_spectral_features_mlp(fbuf, 100000, 3, 4096, 4096, 5, 20.f, fbuf, fbuf, hbuf, 96, 55, 0), -5);
+  EXPECT_TRUE(har_spectral_max_window() >= 2048);
 }
 
 static void tree_contracts() {
