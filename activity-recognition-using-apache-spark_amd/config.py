@@ -58,6 +58,10 @@ class RunConfig:
     # RF over N ranks (torchrun): "tree" = every rank all rows, numTrees / N trees, one all-gather;
     # "data" = row shards + per-level owner reduction; "auto" = tree while the table is small
     rf_parallel: str = "auto"
+    # GBTClassifier (new): multinomial Newton boosting, K trees per round
+    gbt_max_iter: int = 20
+    gbt_max_depth: int = 5
+    gbt_step_size: float = 0.1
     # NaiveBayes / MLP (new)
     nb_model_type: str = "gaussian"
     mlp_hidden: List[int] = field(default_factory=lambda: [128, 128])
@@ -82,6 +86,8 @@ PRESETS: Dict[str, Dict] = {
     "mlp": {"classifiers": ["mlp"], "encoding": "numeric43"},
     # everything the framework offers on the better encoding
     "all-numeric": {"classifiers": ["lr", "dt", "rf", "nb", "mlp"], "encoding": "numeric43", "rf_max_depth": 10},
+    # gradient-boosted trees on the numeric encoding
+    "gbt": {"classifiers": ["gbt"], "encoding": "numeric43"},
 }
 
 

@@ -114,6 +114,14 @@ def _build(md, t, children, device):
                                t["stats"].to(d), t["n_nodes"].numpy(), int(st["max_depth"]))
         C = tr.DecisionTreeClassificationModel if cls.startswith("Decision") else tr.RandomForestClassificationModel
         return C(arrs, md["numFeatures"], md["numClasses"], uid=uid, device=d)
+    if cls == "GBTClassificationModel":
+        from ..models import gbt, tree as tr
+
+        d = _dev(device)
+        arrs = tr.ForestArrays(t["feature"].to(d), t["threshold"].to(d), t["left"].to(d), t["right"].to(d),
+                               t["stats"].to(d), t["n_nodes"].numpy(), int(st["max_depth"]), t["gain"].to(d))
+        return gbt.GBTClassificationModel(arrs, t["init"], md["numFeatures"], md["numClasses"],
+                                          t["loss_history"].tolist(), uid=uid, device=d)
     if cls == "NaiveBayesModel":
         from ..models.naive_bayes import NaiveBayesModel
 

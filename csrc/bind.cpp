@@ -674,6 +674,46 @@ PYBIND11_MODULE(_har_native, m) {
   });
   m.def("spectral_max_window", []() { return har_spectral_max_window(); });
 
+  // gradient-boosted trees (gbt.hip)
+  m.def("gbt_grad", [](u margins, u y, u w, int64_t N, int K, u qgh, u block_loss, u st) {
+    check(har_gbt_grad(P<const float>(margins), P<const int32_t>(y), P<const int32_t>(w), N, K, P<int32_t>(qgh),
+                       P<double>(block_loss), S(st)),
+          "gbt_grad");
+  });
+  m.def("gbt_grad_blocks", [](int64_t N, int K) { return har_gbt_grad_blocks(N, K); });
+  m.def("gbt_hist", [](u bins, u qgh, u w, u node_of, int64_t N, int F, int K, int maxb, int level, u hist, u st) {
+    check(har_gbt_hist(P<const uint8_t>(bins), P<const int32_t>(qgh), P<const int32_t>(w), P<const int32_t>(node_of), N,
+                       F, K, maxb, level, P<int64_t>(hist), S(st)),
+          "gbt_hist");
+  });
+  m.def("gbt_hist_rows_per_block", []() { return har_gbt_hist_rows_per_block(); });
+  m.def("gbt_split", [](u hist, u nbins, u thr_mat, int F, int K, int maxb, int ldthr, int level, int tree0, int maxn,
+                        double lambda, double step, double min_gain, int64_t min_inst, u o_feat, u o_bin, u o_gain,
+                        u o_sums, u feature, u split_bin, u thresh, u left, u right, u gains, u value, u stats, u st) {
+    GbtSplitArgs a{};
+    a.hist = P<const int64_t>(hist);
+    a.nbins = P<const int32_t>(nbins);
+    a.thr_mat = P<const float>(thr_mat);
+    a.F = F; a.K = K; a.maxb = maxb; a.ldthr = ldthr; a.level = level; a.tree0 = tree0; a.maxn = maxn;
+    a.lambda = lambda; a.step = step; a.min_gain = min_gain; a.min_inst = min_inst;
+    a.o_feat = P<int32_t>(o_feat); a.o_bin = P<int32_t>(o_bin); a.o_gain = P<double>(o_gain);
+    a.o_sums = P<int64_t>(o_sums);
+    a.feature = P<int32_t>(feature); a.split_bin = P<int32_t>(split_bin); a.thresh = P<float>(thresh);
+    a.left = P<int32_t>(left); a.right = P<int32_t>(right); a.gains = P<float>(gains); a.value = P<float>(value);
+    a.stats = P<float>(stats);
+    check(har_gbt_split(&a, S(st)), "gbt_split");
+  });
+  m.def("gbt_partition", [](u node_of, u bins, u feature, u split_bin, int64_t N, int F, int K, int level, int tree0,
+                            int maxn, u st) {
+    check(har_gbt_partition(P<int32_t>(node_of), P<const uint8_t>(bins), P<const int32_t>(feature),
+                            P<const int32_t>(split_bin), N, F, K, level, tree0, maxn, S(st)),
+          "gbt_partition");
+  });
+  m.def("gbt_update", [](u margins, u node_of, u value, int64_t N, int K, int tree0, int maxn, u st) {
+    check(har_gbt_update(P<float>(margins), P<const int32_t>(node_of), P<const float>(value), N, K, tree0, maxn, S(st)),
+          "gbt_update");
+  });
+
   m.def("grad_reduce_adam", [](std::vector<u> src, std::vector<int64_t> start, std::vector<int64_t> len,
                                std::vector<int64_t> lds, std::vector<int> nsl, int64_t n, u G, u param, u mm, u vv,
                                u pb, float lr, float b1, float b2, float eps, float wd, u step, int tick, int mode,

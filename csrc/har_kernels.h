@@ -452,6 +452,57 @@ int har_forest_predict(const float* X, int64_t n, int F, int ld, const int32_t* 
                        const int32_t* left, const int32_t* right, const float* leaf, int ntrees, int maxn, int K,
                        int max_depth, int normalize, float* raw_out, hipStream_t s);
 
+// ---- gradient-boosted trees (gbt.hip): multinomial Newton boosting on fixed-point derivatives ----
+// Round m grows K regression trees (one per class) in lock step on the shared uint8 feature-major bins.
+// Derivatives are int32 multiples of 2^-20 (rint), so every histogram / node total is an exact integer sum
+// and a fit is bitwise reproducible.  Trees use the heap layout (children of n: 2n+1, 2n+2); level d holds
+// nodes [2^d - 1, 2^(d+1) - 1).  Contract codes: -2 bad shape (K > 32, depth > 6, bins > 64, sizes), -4 null
+// pointer.
+// margins [N][K] fp32, labels [N], w [N] 0/1 subsample weights (null = 1) -> qgh [K][N][2] int32 (g, h;
+// null = loss only) and block_loss[har_gbt_grad_blocks(N, K)] = per-workgroup sums of -log p_y over ALL rows.
+int har_gbt_grad(const float* margins, const int32_t* y, const int32_t* w, int64_t N, int K, int32_t* qgh,
+                 double* block_loss, hipStream_t s);
+int har_gbt_grad_blocks(int64_t N, int K);
+// Level histograms of all K trees: hist [K][2^level][F][maxb][3] int64 = sums of (g, h, nonzero-weight
+// rows) per (class, node, feature, bin); zeroed here.  |g|, |h| <= 2^20 per row is the caller's contract
+// (har_gbt_grad's outputs satisfy it); N <= 2^26 - 1024
+// (65,535 row chunks of 1,024 rows).
+int har_gbt_hist(const uint8_t* bins, const int32_t* qgh, const int32_t* w, const int32_t* node_of, int64_t N, int F,
+                 int K, int maxb, int level, int64_t* hist, hipStream_t s);
+int har_gbt_hist_rows_per_block();
+typedef struct GbtSplitArgs {
+  const int64_t* hist;     // [K][2^level][F][maxb][3]
+  const int32_t* nbins;    // [F] bins per feature (cuts b in [0, nbins - 2])
+  const float* thr_mat;    // [F][ldthr] thresholds (x <= thr[f][b] goes left)
+  int F, K, maxb, ldthr, level;
+  int tree0, maxn;         // class k writes tree tree0 + k of the [T][maxn] node arrays
+  double lambda, step, min_gain;
+  int64_t min_inst;
+  // the level's decisions [K][2^level]: feature (-1 = leaf), bin, gain, sums = GL, HL, CL, G, H, C
+  int32_t* o_feat;
+  int32_t* o_bin;
+  double* o_gain;
+  int64_t* o_sums;         // [K][2^level][6]
+  // committed node arrays [T][maxn] (stats [T][maxn][K], nonzero only at class k)
+  int32_t* feature;
+  int32_t* split_bin;
+  float* thresh;
+  int32_t* left;
+  int32_t* right;
+  float* gains;
+  float* value;
+  float* stats;
+} GbtSplitArgs;
+// One workgroup per (class tree, node): prefix scan over the bins of every feature, Newton gain in fp64
+// from the exact integers (no contraction), argmax with ties to the lowest feature, then the lowest bin.
+int har_gbt_split(const GbtSplitArgs* a, hipStream_t s);
+// node_of [K][N] of the rows sitting in the level's split nodes moves to the child (weight-0 rows too)
+int har_gbt_partition(int32_t* node_of, const uint8_t* bins, const int32_t* feature, const int32_t* split_bin,
+                      int64_t N, int F, int K, int level, int tree0, int maxn, hipStream_t s);
+// margins[i][k] += value[tree0 + k][node_of[k][i]]
+int har_gbt_update(float* margins, const int32_t* node_of, const float* value, int64_t N, int K, int tree0, int maxn,
+                   hipStream_t s);
+
 // ---- CSV on device (4 KiB chunks per workgroup) ----
 int har_csv_count_newlines(const uint8_t* buf, int64_t n, int32_t* counts, hipStream_t s);
 int har_csv_newline_pos(const uint8_t* buf, int64_t n, const int64_t* block_off, int64_t* pos, hipStream_t s);

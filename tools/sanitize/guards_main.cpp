@@ -150,6 +150,51 @@ static void tree_contracts() {
   EXPECT(har_tree_init(1, 0, 2, 0, 10, cdf, 4, nullptr, ibuf, 1 << 20, fbuf, ibuf, fbuf, 8, ibuf, 0), -2);
 }
 
+static void gbt_contracts() {
+  // boosted trees: more than 32 classes, depth over 6 (levels 0..5), more than 64 bins, null pointers
+  alignas(64) static int64_t lbuf[64];
+  alignas(64) static double dbuf[64];
+  uint8_t bins[16] = {};
+  EXPECT(har_gbt_grad(fbuf, ibuf, nullptr, 10, 33, ibuf, dbuf, 0), -2);
+  EXPECT(har_gbt_grad(fbuf, ibuf, nullptr, 10, 1, ibuf, dbuf, 0), -2);
+  EXPECT(har_gbt_grad(fbuf, ibuf, nullptr, -1, 6, ibuf, dbuf, 0), -2);
+  EXPECT(har_gbt_grad(nullptr, ibuf, nullptr, 10, 6, ibuf, dbuf, 0), -4);
+  EXPECT(har_gbt_grad(fbuf, ibuf, nullptr, 10, 6, ibuf, nullptr, 0), -4);
+  EXPECT(har_gbt_grad(fbuf, ibuf, nullptr, 0, 6, ibuf, dbuf, 0), 0);  // nothing to do
+  EXPECT(har_gbt_hist(bins, ibuf, nullptr, ibuf, 10, 1, 33, 32, 0, lbuf, 0), -2);
+  EXPECT(har_gbt_hist(bins, ibuf, nullptr, ibuf, 10, 1, 6, 32, 6, lbuf, 0), -2);
+  EXPECT(har_gbt_hist(bins, ibuf, nullptr, ibuf, 10, 1, 6, 65, 0, lbuf, 0), -2);
+  EXPECT(har_gbt_hist(bins, ibuf, nullptr, ibuf, int64_t(1) << 27, 1, 6, 32, 0, lbuf, 0), -2);
+  EXPECT(har_gbt_hist(bins, ibuf, nullptr, ibuf, (int64_t(1) << 26) - 1023, 1, 6, 32, 0, lbuf, 0), -2);  // 65,536 row chunks
+  EXPECT(har_gbt_hist(bins, ibuf, nullptr, ibuf, 10, 1, 6, 32, 0, nullptr, 0), -4);
+  EXPECT(har_gbt_hist(nullptr, ibuf, nullptr, ibuf, 10, 1, 6, 32, 0, lbuf, 0), -4);
+  GbtSplitArgs a{};
+  EXPECT(har_gbt_split(nullptr, 0), -4);
+  a.hist = lbuf; a.nbins = ibuf; a.thr_mat = fbuf; a.F = 1; a.K = 6; a.maxb = 32; a.ldthr = 32; a.level = 0;
+  a.tree0 = 0; a.maxn = 127; a.lambda = 1.0; a.step = 0.1; a.min_gain = 0.0; a.min_inst = 1;
+  a.o_feat = ibuf; a.o_bin = ibuf; a.o_gain = dbuf; a.o_sums = lbuf; a.feature = ibuf; a.split_bin = ibuf;
+  a.thresh = fbuf; a.left = ibuf; a.right = ibuf; a.gains = fbuf; a.value = fbuf;  // stats left null
+  EXPECT(har_gbt_split(&a, 0), -4);
+  a.stats = fbuf;
+  a.K = 33;
+  EXPECT(har_gbt_split(&a, 0), -2);
+  a.K = 6; a.level = 6;
+  EXPECT(har_gbt_split(&a, 0), -2);
+  a.level = 5; a.maxb = 65;
+  EXPECT(har_gbt_split(&a, 0), -2);
+  a.maxb = 32; a.maxn = 63;  // level 5's children do not fit 63 nodes
+  EXPECT(har_gbt_split(&a, 0), -2);
+  EXPECT(har_gbt_partition(ibuf, bins, ibuf, ibuf, 10, 1, 33, 0, 0, 127, 0), -2);
+  EXPECT(har_gbt_partition(ibuf, bins, ibuf, ibuf, 10, 1, 6, 6, 0, 127, 0), -2);
+  EXPECT(har_gbt_partition(ibuf, bins, ibuf, ibuf, 10, 1, 6, 5, 0, 63, 0), -2);
+  EXPECT(har_gbt_partition(nullptr, bins, ibuf, ibuf, 10, 1, 6, 0, 0, 127, 0), -4);
+  EXPECT(har_gbt_update(fbuf, ibuf, fbuf, 10, 33, 0, 127, 0), -2);
+  EXPECT(har_gbt_update(fbuf, ibuf, fbuf, 10, 6, 0, 255, 0), -2);
+  EXPECT(har_gbt_update(fbuf, ibuf, nullptr, 10, 6, 0, 127, 0), -4);
+  EXPECT_TRUE(har_gbt_grad_blocks(1000, 6) == 32 && har_gbt_grad_blocks(1, 32) == 1);
+  EXPECT_TRUE(har_gbt_hist_rows_per_block() * (int64_t(1) << 20) < (int64_t(1) << 31));
+}
+
 static void data_contracts() {
   // negative sizes / class counts / ld < columns are rejected before any launch
   int64_t cm[64];
@@ -200,6 +245,7 @@ int main() {
   mlp_contracts();
   window_contracts();
   tree_contracts();
+  gbt_contracts();
   data_contracts();
   sizing_helpers();
   if (g_fail) {
