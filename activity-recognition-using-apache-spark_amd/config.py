@@ -68,6 +68,10 @@ class RunConfig:
     mlp_epochs: int = 60
     mlp_batch: int = 256
     mlp_lr: float = 2e-3
+    # HMMSmoother (new, opt-in): Viterbi-smoothed timeline of every classifier's test predictions
+    hmm: bool = False
+    hmm_sequence_col: str = "USER"
+    hmm_emission: str = "scaled"             # scaled (p / prior) | posterior
     # artefacts
     plots: bool = False
     report: bool = False                   # Results table + charts + index.html (report/summary.py)

@@ -128,6 +128,12 @@ def _build(md, t, children, device):
         d = _dev(device)
         return NaiveBayesModel(t["pi"].to(d), t["theta"].to(d), t["sigma"].to(d) if "sigma" in t else None,
                                st["modelType"], uid=uid, device=d)
+    if cls == "HMMSmootherModel":
+        from ..models.hmm import HMMSmootherModel
+
+        return HMMSmootherModel(t["logA"], t["logpi"], t["prior"], st.get("emission", "scaled"),
+                                p.get("sequenceCol", "USER"), p.get("probabilityCol", "probability"),
+                                p.get("outputCol", "smoothedPrediction"), uid=uid, device=_dev(device))
     if cls == "MultilayerPerceptronClassificationModel":
         from ..models.mlp import MLPEngine, MultilayerPerceptronClassificationModel
 

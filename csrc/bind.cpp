@@ -714,6 +714,17 @@ PYBIND11_MODULE(_har_native, m) {
           "gbt_update");
   });
 
+  // HMM smoothing (hmm.hip)
+  m.def("hmm_chunk_len", []() { return har_hmm_chunk_len(); });
+  m.def("hmm_scan_group", []() { return har_hmm_scan_group(); });
+  m.def("hmm_workspace_bytes", [](int64_t T, int K, int64_t S, int L) { return har_hmm_workspace_bytes(T, K, S, L); });
+  m.def("hmm_viterbi", [](u E, u A, u pi, u off, int64_t T, int K, int64_t nseq, int L, u ws, int64_t ws_bytes, u path,
+                          u score, int phase_lo, int phase_hi, u st) {
+    check(har_hmm_viterbi(P<const int32_t>(E), P<const int32_t>(A), P<const int32_t>(pi), P<const int64_t>(off), T, K, nseq,
+                          L, P<void>(ws), ws_bytes, P<int32_t>(path), P<int64_t>(score), phase_lo, phase_hi, S(st)),
+          "hmm_viterbi");
+  });
+
   m.def("grad_reduce_adam", [](std::vector<u> src, std::vector<int64_t> start, std::vector<int64_t> len,
                                std::vector<int64_t> lds, std::vector<int> nsl, int64_t n, u G, u param, u mm, u vv,
                                u pb, float lr, float b1, float b2, float eps, float wd, u step, int tick, int mode,

@@ -503,6 +503,22 @@ int har_gbt_partition(int32_t* node_of, const uint8_t* bins, const int32_t* feat
 int har_gbt_update(float* margins, const int32_t* node_of, const float* value, int64_t N, int K, int tree0, int maxn,
                    hipStream_t s);
 
+// ---- HMM smoothing (hmm.hip): exact parallel Viterbi over a concatenated batch of sequences ----
+// E [T][K], A [K][K], pi [K] int32 quanta of 2^-20 (|v| <= 2^25, the caller's contract), seq_offsets [S+1] int64
+// on the device (0 = first, T = last, strictly increasing: validated by the caller on the host) -> path [T]
+// int32, score [S] int64 (quanta).  All accumulation is int64 and every max-plus product exact, so the result
+// equals the sequential recurrence bit for bit (lowest-index ties).  L = steps per chunk (har_hmm_chunk_len()
+// is the default); ws = har_hmm_workspace_bytes(T, K, S, L) bytes of device scratch (-1 = bad shape).  Phases
+// phase_lo..phase_hi of 0..6 run (0 flags, 1 chunk matrices, 2 chunk scan, 3 forward, 4 map scan, 5 backtrace,
+// 6 scores; a probe times them one by one over the same workspace).  T = 0 launches nothing.  Contract codes:
+// -2 bad shape (K outside 1..32, T >= 2^31, S outside 1..T, L < 1, workspace too small), -4 null pointer.
+int har_hmm_chunk_len();
+int har_hmm_scan_group();   // chunks per group of the two-level scans: more chunks than this take a second level
+int64_t har_hmm_workspace_bytes(int64_t T, int K, int64_t S, int L);
+int har_hmm_viterbi(const int32_t* E, const int32_t* A, const int32_t* pi, const int64_t* seq_offsets, int64_t T, int K,
+                    int64_t S, int L, void* ws, int64_t ws_bytes, int32_t* path, int64_t* score, int phase_lo,
+                    int phase_hi, hipStream_t s);
+
 // ---- CSV on device (4 KiB chunks per workgroup) ----
 int har_csv_count_newlines(const uint8_t* buf, int64_t n, int32_t* counts, hipStream_t s);
 int har_csv_newline_pos(const uint8_t* buf, int64_t n, const int64_t* block_off, int64_t* pos, hipStream_t s);

@@ -13,6 +13,7 @@ DecisionTree(+CV), RandomForest(+CV) — plus NaiveBayes and an MLP — and writ
     python main.py --preset rf-deep                  # RF 100 trees x depth 10 on the GPU
     python main.py --preset all-numeric --save-models models/
     python main.py --preset gbt --gbt-max-iter 50    # gradient-boosted trees (K trees per round)
+    python main.py --hmm --save-models models/       # + Viterbi-smoothed timeline per classifier (HMMSmoother)
     python main.py --csv-device                      # CSV parsed + dictionary-encoded by the HIP kernels
     python main.py --report                          # + Results table, charts and index.html (report/)
     python main.py --raw raw.csv --hz 20 --window-sec 10 --overlap 0.5   # raw user,activity,timestamp,x,y,z rows
@@ -87,6 +88,8 @@ def run(cfg: RunConfig, ctx=None) -> dict:
                       f"samples ({cfg.window_sec:g} s at {cfg.hz:g} Hz, overlap {cfg.overlap:g})")
         else:
             raw = read_csv(cfg.data, device=dev if (cfg.csv_device and dev.type == "cuda") else None)
+    # the HMM smoother's sequence keys, taken before the feature pipeline prunes the column
+    seq_col = raw[cfg.hmm_sequence_col] if (cfg.hmm and cfg.hmm_sequence_col in raw) else None
     with timer.phase("feature_pipeline"):
         data, pipe_model, df = wisdm.prepare(raw, cfg.encoding)
     section(log, "Data Schema")
@@ -143,6 +146,25 @@ def run(cfg: RunConfig, ctx=None) -> dict:
     plain_rows, cv_rows, records = [], [], {}
     X_test = features_tensor(test_data, "features", dev)
     y_test = torch.as_tensor(test_data["label"].data.astype(np.int64), device=dev)
+    smoother = test_offsets = None
+    if cfg.hmm:  # transitions of the training rows in table order; the test rows keep their table order too
+        from har.data.split import split_ids
+        from har.models.hmm import HMMSmoother, offsets_of_keys
+        from har.ops.hmm import count_segments
+
+        ids = split_ids(df.count(), cfg.split, cfg.seed)  # the partition random_split made above
+
+        def seq_offsets(bucket, n):
+            if seq_col is None:
+                return torch.tensor([0, n], dtype=torch.int64)
+            return offsets_of_keys(seq_col.take_rows(np.nonzero(ids == bucket)[0]))
+
+        hmm_est = HMMSmoother(sequenceCol=cfg.hmm_sequence_col, labelCol="label", emission=cfg.hmm_emission,
+                              numClasses=n_classes, device=dev)
+        with timer.phase("fit:hmm"):
+            smoother = hmm_est.fit_labels(torch.as_tensor(train["label"].data.astype(np.int64)),
+                                          seq_offsets(0, train.count()), n_classes)
+        test_offsets = seq_offsets(1, test.count())
     for name in cfg.classifiers:
         est = make_estimator(name, cfg, dev, n_features, n_classes)
         with timer.phase(f"fit:{name}"), data_parallel(ctx):
@@ -165,15 +187,27 @@ def run(cfg: RunConfig, ctx=None) -> dict:
         with timer.phase(f"evaluate:{name}"):
             r = evaluate_all(y_test, pred, raw_pred, n_classes)
         evaluation_block(log, r)
+        hmm_rec = {}
+        if smoother is not None:
+            with timer.phase(f"smooth:{name}"):
+                path, _ = smoother.decode(prob, test_offsets)
+            hmm_rec = {"smoothed_accuracy": float((path.long() == y_test).double().mean()),
+                       "segments": count_segments(path, test_offsets),
+                       "raw_segments": count_segments(pred.to(torch.int32), test_offsets)}
+            log.print("HMM smoothed Accuracy = %g  (%d segments, %d before smoothing; %d sequences)"
+                      % (hmm_rec["smoothed_accuracy"], hmm_rec["segments"], hmm_rec["raw_segments"],
+                         test_offsets.numel() - 1))
         row = (csvout.cv_row if name.endswith("cv") else csvout.plain_row)(str(model), r, train_s, test_s)
         (cv_rows if name.endswith("cv") else plain_rows).append(row)
         records[name] = {"model": str(model), "train_s": train_s, "predict_s": test_s,
                          "train_windows_per_s": train.count() / max(train_s, 1e-9),
-                         "predict_windows_per_s": test.count() / max(test_s, 1e-9), **r.as_dict()}
+                         "predict_windows_per_s": test.count() / max(test_s, 1e-9), **r.as_dict(), **hmm_rec}
         if cfg.save_models and main_rank:
             persist.save(model, os.path.join(cfg.save_models, name), labels=vocab)
     if cfg.save_models and main_rank:
         persist.save(pipe_model, os.path.join(cfg.save_models, "pipeline"), labels=vocab)
+        if smoother is not None:
+            persist.save(smoother, os.path.join(cfg.save_models, "hmm"), labels=vocab)
     world = ctx.world_size if ctx is not None else 1
     if not main_rank:
         log.close()

@@ -12,8 +12,14 @@ throughput with device-synchronized timers.
     python main.py --preset all-numeric --save-models models/
     python predict.py --models models/ --model rf --data new_windows.csv --out preds.csv
     python predict.py --models models/ --model mlp --data wisdm_data.csv --csv-device --repeat 20
+    python predict.py --models models/ --model rf --smooth hmm --segments-out timeline.csv --out preds.csv
 
 Output CSV columns: ``row, UID (if present), prediction, label_name, probability``.
+``--smooth hmm`` (needs ``<models>/hmm``, written by ``main.py --hmm --save-models``) decodes the
+predictions of every sequence (runs of equal ``--sequence-col`` values, in row order) with the saved
+HMMSmoother: the CSV gains ``smoothed_prediction, smoothed_label_name``, the JSON record ``smooth_s``,
+``segments`` (and ``smoothed_accuracy`` for labelled input), and ``--segments-out FILE`` writes the
+timeline ``sequence, first_row, last_row, state, label_name``.
 When the input still has the ``ACTIVITY`` column the script also prints the
 reference's evaluation block (accuracy, weighted F1, ...).  Rows whose string
 categories were never seen at training time are rejected by the indexers unless
@@ -63,6 +69,11 @@ def run(args) -> dict:
     with open(os.path.join(args.models, args.model, "metadata.json")) as f:
         labels = json.load(f).get("labels")
     model = getattr(model, "bestModel", model)
+    smoother = None
+    if args.smooth:
+        if args.smooth != "hmm":
+            raise ValueError(f"unknown smoother {args.smooth!r} (hmm)")
+        smoother = persist.load(os.path.join(args.models, "hmm"), device=dev)
     t0 = time.perf_counter()
     raw = read_csv(args.data, device=dev if (args.csv_device and dev.type == "cuda") else None)
     table = encode(pipe, raw, args.handle_invalid)
@@ -86,16 +97,44 @@ def run(args) -> dict:
         y = torch.as_tensor(table["label"].data.astype(np.int64), device=dev)
         r = evaluate_all(y, pred, raw_pred, int(raw_pred.shape[1]))
         rec.update({"accuracy": r.accuracy, "f1": r.f1})
+    sp = None
+    if smoother is not None:
+        from har.models.hmm import sequence_offsets
+        from har.ops.hmm import segments
+
+        if table.count() != raw.count():
+            raise ValueError("--smooth needs every input row (no --handle-invalid skip): the sequences are runs of rows")
+        offsets = sequence_offsets(raw, args.sequence_col or smoother.sequenceCol)
+        device_sync(dev)
+        t2 = time.perf_counter()
+        path, _ = smoother.decode(prob, offsets)
+        device_sync(dev)
+        rec["smooth_s"] = round(time.perf_counter() - t2, 6)
+        segs = segments(path, offsets)
+        rec["segments"] = len(segs)
+        sp = path.long().cpu().numpy()
+        if "label" in table.columns:
+            rec["smoothed_accuracy"] = float((sp == table["label"].data.astype(np.int64)).mean())
+        if args.segments_out:
+            with open(args.segments_out, "w", newline="") as f:
+                w = csv.writer(f)
+                w.writerow(["sequence", "first_row", "last_row", "state", "label_name"])
+                for q, a, b, k in segs:
+                    w.writerow([q, a, b, k, labels[k] if labels and k < len(labels) else ""])
     if args.out:
         p = pred.long().cpu().numpy()
         pr = prob.float().cpu().numpy()
         uid = table["UID"].data if "UID" in table.columns else None
         with open(args.out, "w", newline="") as f:
             w = csv.writer(f)
-            w.writerow(["row"] + (["UID"] if uid is not None else []) + ["prediction", "label_name", "probability"])
+            w.writerow(["row"] + (["UID"] if uid is not None else []) + ["prediction", "label_name", "probability"]
+                       + (["smoothed_prediction", "smoothed_label_name"] if sp is not None else []))
             for i in range(n):
                 name = labels[p[i]] if labels and p[i] < len(labels) else ""
-                w.writerow([i] + ([int(uid[i])] if uid is not None else []) + [int(p[i]), name, float(pr[i, p[i]])])
+                extra = []
+                if sp is not None:
+                    extra = [int(sp[i]), labels[sp[i]] if labels and sp[i] < len(labels) else ""]
+                w.writerow([i] + ([int(uid[i])] if uid is not None else []) + [int(p[i]), name, float(pr[i, p[i]])] + extra)
     return rec
 
 
@@ -109,6 +148,9 @@ def main(argv=None):
     ap.add_argument("--csv-device", action="store_true", help="parse the CSV with the HIP kernels")
     ap.add_argument("--repeat", type=int, default=1, help="timed prediction passes (throughput)")
     ap.add_argument("--handle-invalid", default="error", choices=["error", "skip", "keep"])
+    ap.add_argument("--smooth", default="", help="hmm: Viterbi-smooth the predictions with <models>/hmm")
+    ap.add_argument("--sequence-col", default="", help="column whose runs are the sequences (default: the saved one)")
+    ap.add_argument("--segments-out", default="", help="with --smooth: write the timeline's segments to this CSV")
     rec = run(ap.parse_args(argv))
     print(json.dumps(rec))
     return rec
