@@ -72,6 +72,11 @@ class RunConfig:
     hmm: bool = False
     hmm_sequence_col: str = "USER"
     hmm_emission: str = "scaled"             # scaled (p / prior) | posterior
+    # KMeans + silhouette ClusteringEvaluator (new, opt-in): --kmeans K clusters the training rows' dense
+    # numeric features after the classifiers
+    kmeans: int = 0
+    kmeans_max_iter: int = 20
+    kmeans_init: str = "k-means++"           # k-means++ | random
     # artefacts
     plots: bool = False
     report: bool = False                   # Results table + charts + index.html (report/summary.py)

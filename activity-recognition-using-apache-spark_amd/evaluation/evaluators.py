@@ -72,6 +72,39 @@ class RegressionEvaluator(Evaluator):
         return self.metricName in ("r2", "var")
 
 
+class ClusteringEvaluator(Evaluator):
+    """Spark's ``ClusteringEvaluator``: the mean squared-Euclidean silhouette of ``predictionCol`` over
+    ``featuresCol`` (``har/ops/kmeans.py`` defines it; on a GPU it runs the silhouette kernel)."""
+
+    def __init__(self, featuresCol="features", predictionCol="prediction", metricName="silhouette",
+                 distanceMeasure="squaredEuclidean", device=None):
+        if metricName != "silhouette" or distanceMeasure != "squaredEuclidean":
+            raise ValueError("ClusteringEvaluator supports metricName='silhouette' with "
+                             "distanceMeasure='squaredEuclidean'")
+        self.featuresCol, self.predictionCol, self.metricName = featuresCol, predictionCol, metricName
+        self.distanceMeasure, self.device = distanceMeasure, device
+
+    def evaluate_tensors(self, X, pred, k: Optional[int] = None) -> float:
+        import torch
+
+        from ..ops import kmeans as KM
+
+        pred = torch.as_tensor(pred).to(device=X.device, dtype=torch.int64)
+        if k is None:
+            k = int(pred.max()) + 1 if pred.numel() else 1
+        if pred.numel() and (int(pred.min()) < 0 or int(pred.max()) >= k):
+            raise ValueError(f"ClusteringEvaluator: predictions outside [0, {k})")
+        KM.check_native_range(k, X.shape[1])
+        return float(KM.silhouette(X, pred, int(k)))
+
+    def evaluate(self, table: Table, params=None) -> float:
+        from ..models.base import features_tensor, labels_tensor, resolve_device
+
+        dev = resolve_device(self.device)
+        X = features_tensor(table, self.featuresCol, dev)
+        return self.evaluate_tensors(X, labels_tensor(table, self.predictionCol, dev))
+
+
 @dataclass
 class MetricsRecord:
     """Every number one reference evaluation block prints."""

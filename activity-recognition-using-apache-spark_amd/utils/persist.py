@@ -128,6 +128,14 @@ def _build(md, t, children, device):
         d = _dev(device)
         return NaiveBayesModel(t["pi"].to(d), t["theta"].to(d), t["sigma"].to(d) if "sigma" in t else None,
                                st["modelType"], uid=uid, device=d)
+    if cls == "KMeansModel":
+        from ..models.kmeans import KMeansModel
+
+        m = KMeansModel.from_state(t, uid=uid, device=_dev(device))
+        m.featuresCol = p.get("featuresCol", m.featuresCol)
+        m.predictionCol = p.get("predictionCol", m.predictionCol)
+        m.feature_cols = st.get("feature_cols")
+        return m
     if cls == "HMMSmootherModel":
         from ..models.hmm import HMMSmootherModel
 

@@ -725,6 +725,69 @@ PYBIND11_MODULE(_har_native, m) {
           "hmm_viterbi");
   });
 
+  // K-means and the silhouette (kmeans.hip)
+  m.def("kmeans_rows_per_block", []() { return har_kmeans_rows_per_block(); });
+  m.def("kmeans_max_k", []() { return har_kmeans_max_k(); });
+  m.def("kmeans_max_d", []() { return har_kmeans_max_d(); });
+  m.def("kmeans_plan", [](int D, int K) {
+    int o[4] = {0, 0, 0, 0};
+    check(har_kmeans_plan(D, K, o), "kmeans_plan");
+    return std::vector<int>{o[0], o[1], o[2], o[3]};
+  });
+  m.def("kmeans_assign", [](u X, int64_t N, int D, int K, u C, u h, u w, u labels, u scale, u norm_scale, u assign,
+                            u d2, u acc, u part, u st) {
+    KMeansArgs a{};
+    a.X = P<const float>(X);
+    a.N = N;
+    a.D = D;
+    a.K = K;
+    a.C = P<const float>(C);
+    a.h = P<const float>(h);
+    a.w = P<const int32_t>(w);
+    a.labels = P<const int32_t>(labels);
+    a.scale = P<const float>(scale);
+    a.norm_scale = P<const double>(norm_scale);
+    a.assign = P<int32_t>(assign);
+    a.d2 = P<float>(d2);
+    a.acc = P<int64_t>(acc);
+    a.part = P<double>(part);
+    check(har_kmeans_assign(&a, S(st)), "kmeans_assign");
+  });
+  m.def("kmeans_silhouette", [](u X, int64_t N, int D, int K, u M, u h, u labels, u cnt, u sil, u part, u st) {
+    KMeansArgs a{};
+    a.X = P<const float>(X);
+    a.N = N;
+    a.D = D;
+    a.K = K;
+    a.C = P<const float>(M);
+    a.h = P<const float>(h);
+    a.labels = P<const int32_t>(labels);
+    a.cnt = P<const double>(cnt);
+    a.sil = P<float>(sil);
+    a.part = P<double>(part);
+    check(har_kmeans_silhouette(&a, S(st)), "kmeans_silhouette");
+  });
+  m.def("kmeans_update", [](u acc, u scale, int K, int D, u cost, int ncost, int max_iter, double tol2, u C, u Cnew, u h,
+                            u state, u cost_hist, u moved, u sizes, u st) {
+    KMeansUpdateArgs a{};
+    a.acc = P<int64_t>(acc);
+    a.scale = P<const float>(scale);
+    a.K = K;
+    a.D = D;
+    a.cost = P<const double>(cost);
+    a.ncost = ncost;
+    a.max_iter = max_iter;
+    a.tol2 = tol2;
+    a.C = P<float>(C);
+    a.Cnew = P<float>(Cnew);
+    a.h = P<float>(h);
+    a.state = P<int32_t>(state);
+    a.cost_hist = P<double>(cost_hist);
+    a.moved = P<double>(moved);
+    a.sizes = P<int64_t>(sizes);
+    check(har_kmeans_update(&a, S(st)), "kmeans_update");
+  });
+
   m.def("grad_reduce_adam", [](std::vector<u> src, std::vector<int64_t> start, std::vector<int64_t> len,
                                std::vector<int64_t> lds, std::vector<int> nsl, int64_t n, u G, u param, u mm, u vv,
                                u pb, float lr, float b1, float b2, float eps, float wd, u step, int tick, int mode,

@@ -519,6 +519,57 @@ int har_hmm_viterbi(const int32_t* E, const int32_t* A, const int32_t* pi, const
                     int64_t S, int L, void* ws, int64_t ws_bytes, int32_t* path, int64_t* score, int phase_lo,
                     int phase_hi, hipStream_t s);
 
+// ---- K-means and the silhouette (kmeans.hip): rows x centres on the fp32 matrix cores ----
+// Working rows X [N][D] fp32 (centred by the caller), operand rows C [K][D] with h [K]: the score is
+// s[n][k] = h[k] - <X[n], C[k]> (assignment: C = centres, h = ||C||^2 / 2; silhouette: C = cluster means,
+// h = mean ||x||^2 of the cluster / 2).  K and D in 1..har_kmeans_max_k() / har_kmeans_max_d().
+// Contract codes: -2 bad shape or a combination of outputs the mode does not have, -4 null pointer.
+typedef struct KMeansArgs {
+  const float* X;
+  int64_t N;
+  int D, K;
+  const float* C;         // [K][D]
+  const float* h;         // [K]
+  const int32_t* w;       // assignment: integer row weights >= 0 (null = 1; 0 = the row is ignored)
+  const int32_t* labels;  // assignment: given clusters [N] — no product, accumulation only (assign, d2, part
+                          // must be null; a label outside [0, K) is ignored); silhouette: the rows' clusters
+  const float* scale;     // [D] 2^e[f] (with acc)
+  const double* norm_scale;  // [1] on the device: 2^q of the norm channel (with acc)
+  int32_t* assign;        // [N] argmin_k s, lowest k among equals (nullable)
+  float* d2;              // [N] float(max(0, ||x||^2 + 2 s)) (nullable)
+  int64_t* acc;           // [K D sums | K counts | K norms], ADDED to (the caller or har_kmeans_update zeroes it)
+  double* part;           // [ceil(N / har_kmeans_rows_per_block())] per-workgroup sums of w d2 / of the silhouettes
+  const double* cnt;      // silhouette: cluster sizes [K]
+  float* sil;             // silhouette: per row (nullable)
+} KMeansArgs;
+int har_kmeans_assign(const KMeansArgs* a, hipStream_t s);
+int har_kmeans_silhouette(const KMeansArgs* a, hipStream_t s);
+int har_kmeans_rows_per_block();
+int har_kmeans_max_k();
+int har_kmeans_max_d();
+// out4 = {centres per LDS slab, slabs, 1 if the accumulators go through LDS, LDS bytes}
+int har_kmeans_plan(int D, int K, int* out4);
+// One Lloyd update in one launch.  state = {iterations, converged} (device).  When not converged and
+// iterations < max_iter: C_new[k][f] = float(double(sum) * 2^-e[f] / count[k]) (an empty cluster keeps its
+// centre), h, moved = max_k ||C_new[k] - C[k]||^2, cost_hist[iterations] = the sum of cost[0 .. ncost) in
+// order, sizes = the counts, iterations += 1, converged = moved <= tol2.  Otherwise none of those change.
+// In both cases acc is zeroed for the next assignment.
+typedef struct KMeansUpdateArgs {
+  int64_t* acc;           // [K D | K | K]
+  const float* scale;     // [D] 2^e[f]
+  int K, D, ncost, max_iter;
+  const double* cost;     // [ncost] cost partials of the assignment that filled acc
+  double tol2;
+  float* C;               // [K][D]
+  float* Cnew;            // [K][D] scratch
+  float* h;               // [K]
+  int32_t* state;         // [2]
+  double* cost_hist;      // [max_iter]
+  double* moved;          // [1] (nullable)
+  int64_t* sizes;         // [K] (nullable)
+} KMeansUpdateArgs;
+int har_kmeans_update(const KMeansUpdateArgs* a, hipStream_t s);
+
 // ---- CSV on device (4 KiB chunks per workgroup) ----
 int har_csv_count_newlines(const uint8_t* buf, int64_t n, int32_t* counts, hipStream_t s);
 int har_csv_newline_pos(const uint8_t* buf, int64_t n, const int64_t* block_off, int64_t* pos, hipStream_t s);

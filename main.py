@@ -14,6 +14,7 @@ DecisionTree(+CV), RandomForest(+CV) — plus NaiveBayes and an MLP — and writ
     python main.py --preset all-numeric --save-models models/
     python main.py --preset gbt --gbt-max-iter 50    # gradient-boosted trees (K trees per round)
     python main.py --hmm --save-models models/       # + Viterbi-smoothed timeline per classifier (HMMSmoother)
+    python main.py --kmeans 6 --save-models models/  # + KMeans clusters, silhouette, purity against the labels
     python main.py --csv-device                      # CSV parsed + dictionary-encoded by the HIP kernels
     python main.py --report                          # + Results table, charts and index.html (report/)
     python main.py --raw raw.csv --hz 20 --window-sec 10 --overlap 0.5   # raw user,activity,timestamp,x,y,z rows
@@ -67,6 +68,42 @@ def make_estimator(name: str, cfg: RunConfig, dev, n_features: int, n_classes: i
                              maxDepth=cfg.gbt_max_depth, stepSize=cfg.gbt_step_size, maxBins=cfg.max_bins,
                              seed=cfg.seed, device=dev)
     return build_estimator(name, cfg, dev, n_features, n_classes)
+
+
+def run_kmeans(cfg: RunConfig, dev, ctx, train, test, vocab, timer, log, main_rank) -> dict:
+    """``--kmeans K``: cluster the training rows' dense numeric features, then the block of result.txt —
+    sizes, cost, iterations, silhouette on the test rows, purity and the cluster-by-label table."""
+    from har.evaluation.evaluators import ClusteringEvaluator
+    from har.models.kmeans import KMeans, kmeans_feature_cols, table_features
+
+    cols = kmeans_feature_cols(cfg.encoding)
+    X_train, X_test = table_features(train, cols, dev), table_features(test, cols, dev)
+    y_train = torch.as_tensor(train["label"].data.astype(np.int64), device=dev)
+    est = KMeans(k=cfg.kmeans, maxIter=cfg.kmeans_max_iter, initMode=cfg.kmeans_init, seed=cfg.seed, device=dev)
+    with timer.phase("fit:kmeans"), data_parallel(ctx):
+        model = est.fit_features(X_train)
+    model.feature_cols = cols
+    train_s = round(timer.get("fit:kmeans"), 6)
+    with timer.phase("evaluate:kmeans"):
+        cm, majority, purity = model.label_map(model.predict(X_train), y_train, len(vocab))
+        pred_test = model.predict(X_test)
+        sil = ClusteringEvaluator(device=dev).evaluate_tensors(X_test, pred_test, model.k) if X_test.shape[0] else 0.0
+    s = model.summary
+    section(log, "KMeans")
+    log.print(f"{model} trained in {train_s} seconds ({X_train.shape[1]} features, init {cfg.kmeans_init})")
+    log.print("Cluster Sizes      = " + str(s.clusterSizes))
+    log.print("Training Cost      = %g" % s.trainingCost)
+    log.print("Iterations         = %d (converged: %s)" % (s.numIter, s.converged))
+    log.print("Silhouette (test)  = %g" % sil)
+    log.print("Purity (train)     = %g" % purity)
+    log.print("Cluster x label (rows: clusters; columns: " + ", ".join(str(v) for v in vocab) + ")")
+    for c, row in enumerate(cm.tolist()):
+        log.print("  %3d -> %-12s %s" % (c, vocab[int(majority[c])], row))
+    if cfg.save_models and main_rank:
+        persist.save(model, os.path.join(cfg.save_models, "kmeans"), labels=vocab)
+    return {"model": str(model), "k": model.k, "train_s": train_s, "training_cost": s.trainingCost,
+            "num_iter": s.numIter, "converged": s.converged, "cluster_sizes": s.clusterSizes, "silhouette": sil,
+            "purity": purity, "contingency": cm.tolist(), "majority_labels": model.majority_labels}
 
 
 def run(cfg: RunConfig, ctx=None) -> dict:
@@ -137,6 +174,15 @@ def run(cfg: RunConfig, ctx=None) -> dict:
                 wm = est.fit(small)
                 wm.predict_all(wm.features_input(test_data))
                 device_sync(dev)
+            if cfg.kmeans:  # the K-means / silhouette code objects, on 256 rows and 2 iterations
+                from har.evaluation.evaluators import ClusteringEvaluator
+                from har.models.kmeans import KMeans, kmeans_feature_cols, table_features
+
+                Xs = table_features(train.head(min(256, train.count())), kmeans_feature_cols(cfg.encoding), dev)
+                wk = KMeans(k=min(cfg.kmeans, Xs.shape[0]), maxIter=2, initMode=cfg.kmeans_init, seed=cfg.seed,
+                            device=dev).fit_features(Xs)
+                ClusteringEvaluator(device=dev).evaluate_tensors(Xs, wk.predict(Xs), wk.k)
+                device_sync(dev)
         # not part of any "trained in" time below (the reference's timers exclude SparkContext start-up too)
         log.print("Device warm-up (HIP code objects, allocator) %.6f seconds" % timer.get("device_warmup"))
     log.print(BANNER_CLASSIFY)
@@ -204,6 +250,9 @@ def run(cfg: RunConfig, ctx=None) -> dict:
                          "predict_windows_per_s": test.count() / max(test_s, 1e-9), **r.as_dict(), **hmm_rec}
         if cfg.save_models and main_rank:
             persist.save(model, os.path.join(cfg.save_models, name), labels=vocab)
+    kmeans_rec = None
+    if cfg.kmeans:
+        kmeans_rec = run_kmeans(cfg, dev, ctx, train, test, vocab, timer, log, main_rank)
     if cfg.save_models and main_rank:
         persist.save(pipe_model, os.path.join(cfg.save_models, "pipeline"), labels=vocab)
         if smoother is not None:
@@ -222,6 +271,8 @@ def run(cfg: RunConfig, ctx=None) -> dict:
     summary = {"device": str(dev), "world_size": world, "encoding": cfg.encoding, "n_train": train.count(), "n_test": test.count(),
                "seed": cfg.seed, "wall_s": time.perf_counter() - t_run, "models": records,
                "phases_s": {k: round(v, 6) for k, v in timer.as_dict().items()}}
+    if kmeans_rec is not None:
+        summary["kmeans"] = kmeans_rec
     csvout.append_jsonl(os.path.join(cfg.out_dir, "metrics.jsonl"), summary)
     log.close()
     if cfg.report:

@@ -77,6 +77,8 @@ def run(args) -> dict:
     t0 = time.perf_counter()
     raw = read_csv(args.data, device=dev if (args.csv_device and dev.type == "cuda") else None)
     table = encode(pipe, raw, args.handle_invalid)
+    if type(model).__name__ == "KMeansModel":
+        return run_kmeans(args, model, table, labels, dev, t0)
     X = features_tensor(table, "features", dev)
     device_sync(dev)
     t_ingest = time.perf_counter() - t0
@@ -138,10 +140,49 @@ def run(args) -> dict:
     return rec
 
 
+def run_kmeans(args, model, table, labels, dev, t0) -> dict:
+    """``--model kmeans``: the cluster id per row and, when the saved model carries a label map, the
+    majority label of that cluster."""
+    from har.models.kmeans import table_features
+
+    X = table_features(table, model.feature_cols, dev)
+    device_sync(dev)
+    t_ingest = time.perf_counter() - t0
+    pred = model.predict(X)  # warm-up (code objects, allocator)
+    device_sync(dev)
+    t1 = time.perf_counter()
+    for _ in range(args.repeat):
+        pred = model.predict(X)
+    device_sync(dev)
+    t_pred = (time.perf_counter() - t1) / max(1, args.repeat)
+    n = X.shape[0]
+    rec = {"model": str(model), "rows": n, "device": str(dev), "ingest_encode_s": round(t_ingest, 6),
+           "predict_s": round(t_pred, 6), "predict_windows_per_s": n / max(t_pred, 1e-12),
+           "clusters_used": int(torch.unique(pred).numel())}
+    maj = model.majority_labels
+    if maj is not None and "label" in table.columns:
+        y = torch.as_tensor(table["label"].data.astype(np.int64), device=dev)
+        rec["majority_label_accuracy"] = float((torch.as_tensor(maj, device=dev)[pred] == y).double().mean())
+    if args.out:
+        p = pred.long().cpu().numpy()
+        uid = table["UID"].data if "UID" in table.columns else None
+        with open(args.out, "w", newline="") as f:
+            w = csv.writer(f)
+            w.writerow(["row"] + (["UID"] if uid is not None else []) + ["cluster"]
+                       + (["majority_label", "label_name"] if maj is not None else []))
+            for i in range(n):
+                extra = []
+                if maj is not None:
+                    k = maj[p[i]]
+                    extra = [k, labels[k] if labels and k < len(labels) else ""]
+                w.writerow([i] + ([int(uid[i])] if uid is not None else []) + [int(p[i])] + extra)
+    return rec
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="Batch inference from models saved by main.py --save-models")
     ap.add_argument("--models", required=True, help="directory written by main.py --save-models")
-    ap.add_argument("--model", default="rf", help="sub-directory name: lr, lrcv, dt, dtcv, rf, rfcv, nb, mlp, gbt")
+    ap.add_argument("--model", default="rf", help="sub-directory name: lr, lrcv, dt, dtcv, rf, rfcv, nb, mlp, gbt, kmeans")
     ap.add_argument("--data", default=DEFAULT_WISDM)
     ap.add_argument("--out", default="")
     ap.add_argument("--device", default="auto")
