@@ -616,8 +616,11 @@ def _enqueue_fit(b: "ForestBuilder", bufs: dict, y32, rw, row_offset: int, N: in
 
 def _finish_fit(b: "ForestBuilder", bufs: dict, nn, clone: bool) -> ForestArrays:
     h = torch.cat([nn, bufs["bad"]]).cpu().numpy()  # the fit's one device -> host read
-    if h[-1] != 0:
+    if h[-1] & 1:
         raise ValueError("labels out of range")
+    if h[-1] & 2:  # tree_init: bootstrap x row weight (the level kernels count in uint32)
+        raise ValueError("row weights on the device path must be non-negative integers below 2^24 "
+                         "(a fractional row_weight would be truncated in the histograms)")
     Tn, maxn = bufs["feature"].shape
     o = _out_views(bufs["out"].clone(), Tn, maxn, b.K) if clone else bufs
     return ForestArrays(o["feature"], o["thresh"], o["left"], o["right"], o["stats"], h[:-1].astype(np.int64), b.D,

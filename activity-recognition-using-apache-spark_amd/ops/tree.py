@@ -452,7 +452,10 @@ def hist_split_native(bins, nbins_feat, label, rows, row_w, node_start, node_cou
     """Fused LDS histogram + split on one device; in data parallel the kernel runs twice:
     histogram-only into a [A, m, bins, K] buffer, then either one RCCL all-reduce of it and
     split search for every node (``allreduce``), or a reduce-scatter by node owner, split
-    search for the owned nodes and an all-gather of the winners (``owner``)."""
+    search for the owned nodes and an all-gather of the winners (``owner``).
+
+    Integer-weight contract: ``row_w`` holds non-negative integers and every class sum stays below
+    2^24 — the kernel adds the weights as uint32, so a fractional weight would be truncated."""
     A, m = feats.shape
     F, N = bins.shape
     fc = max(1, min(m, LDS_BUDGET // (max_bins * K * 4)))
@@ -537,7 +540,10 @@ def hist_split_planned(bins, nbins_feat, label, rows, row_w, node_start, node_co
     is kept there for the next level; with ``derive_from`` / ``parent_of`` (the previous level's
     frontier output) and ``hprev`` (the previous level's store) the nodes marked
     ``derive_from[a] >= 0`` — the heavier of two candidate siblings, whose rows the grouping skipped —
-    take parent - sibling instead of a pass over their rows (exact: integer-valued weights)."""
+    take parent - sibling instead of a pass over their rows (exact: integer-valued weights).
+
+    Integer-weight contract: as ``hist_split_native`` — ``row_w`` holds non-negative integers, sums
+    below 2^24; the chunk merges and the subtraction are exact only then."""
     A, m = feats.shape
     F, N = bins.shape
     fc = max(1, min(m, LDS_BUDGET // (max_bins * K * 4)))
@@ -757,7 +763,8 @@ def forest_predict_native(X, feature, threshold, left, right, leaf_stats, max_de
     N, F = X.shape
     K = leaf_stats.shape[-1]
     out = torch.zeros(N, K, dtype=torch.float32, device=X.device)
-    _native.kernels().forest_predict(X.contiguous().data_ptr(), N, F, X.stride(0), feature.data_ptr(),
+    Xc = X.contiguous()  # (a sliced view: the copy's own leading dimension, not the parent's)
+    _native.kernels().forest_predict(Xc.data_ptr(), N, F, Xc.stride(0), feature.data_ptr(),
                                      threshold.data_ptr(), left.data_ptr(), right.data_ptr(), leaf_stats.data_ptr(),
                                      T, maxn, K, max_depth, int(normalize), out.data_ptr(), _native.stream_ptr())
     return out

@@ -155,8 +155,9 @@ int har_cast_pad_bf16(const float* in, int rows, int cols_in, int ld_in, uint16_
 int har_philox_buckets(uint64_t seed, uint32_t stream, int64_t row0, int64_t n, const uint32_t* thr,
                        int nthr, int32_t* out, hipStream_t s);
 // Per-fit init (tree.hip): W [T][N] = bootstrap draw from the CDF table (or 1) x optional rw [T][N]; node_of [T][N]
-// = 0 / -1 (zero weight); root class counts added into stats + t * stats_tree_stride; *bad = 1 on a
-// label outside [0, K).
+// = 0 / -1 (zero weight); root class counts added into stats + t * stats_tree_stride; *bad |= 1 on a
+// label outside [0, K), *bad |= 2 on a weight W that is not a non-negative integer below 2^24 (the
+// integer-weight contract of the level kernels, see "trees" below).
 // cdf: HOST array of ncdf (<= 16) uint32 bootstrap CDF thresholds (ncdf = 0: every weight 1).
 int har_tree_init(uint64_t seed, int tree0, int ntrees, int64_t row0, int64_t n, const uint32_t* cdf, int ncdf,
                   const float* rw, const int32_t* y, int K, float* W, int32_t* node_of, float* stats,
@@ -368,6 +369,9 @@ int har_spectral_max_window();
 // out_total [A][K] = node class counts.  mode 0 fused; 1 histogram only -> ghist [A][m][maxbins][K];
 // 2 split search from ghist (after a cross-rank reduction).  row_chunks > 1 (mode 1 only): each node's
 // rows are split over that many workgroups that atomically merge into a ZEROED ghist.
+// Integer-weight contract: every row_w is a non-negative integer and every class sum stays below 2^24.
+// The histograms accumulate the weights as uint32 (a fractional weight would be truncated), and the
+// order-free merges, sibling subtraction and the packed DP wire rely on the sums being exact.
 // One-hot-aware histograms (tree.hip SPARSE): cat [N][ncat] int32 = the global column of each row's 1 in
 // every one-hot block (-1 none), onehot [F] uint8 = 1 for the one-hot columns; F = the feature count.
 typedef struct TreeSparse {

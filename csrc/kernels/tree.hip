@@ -24,6 +24,18 @@ constexpr int KMAX = 32;
 #define HIST_UNROLL 4
 #endif
 
+// Entropy of a side of weight w > 0 from q = sum c log2 c: (w log2 w - q) / w.  Taken in this form, not
+// as log2 w - q / w: for a single-class side w log2 w and q are the same product, so the impurity is
+// exactly 0 — a pure node's gains are all exactly 0 and the lowest (slot, bin) wins, as in the CPU
+// oracle — where (w log2 w) / w need not round back to log2 w and left gains of +-1e-16 whose maximum
+// picked an arbitrary threshold.  The product is rounded on its own, as the one q holds: contraction
+// is off here, since fma(w, log2 w, -q) would keep the product's rounding error as the difference.
+__device__ __forceinline__ double ent_imp(double w, double q) {
+#pragma clang fp contract(off)
+  const double p = w * log2(w);
+  return (p - q) / w;
+}
+
 // Split search of TWO feature slots per wave (maxBins <= 32): lanes 0..31 hold the bins of slot
 // 2p, lanes 32..63 those of slot 2p + 1.  KC class prefix sums at a time advance together through
 // ONE 5-step scan over the 32-lane halves (independent shuffles pipeline), instead of a dependent
@@ -82,7 +94,7 @@ __device__ __forceinline__ void split_search_pairs(const float* hist, const int*
       if (impurity == 0) {
         ip = 1.0 - qt / (wt * wt); il = 1.0 - ql / (wl * wl); ir = 1.0 - qr / (wr * wr);
       } else {
-        ip = log2(wt) - qt / wt; il = log2(wl) - ql / wl; ir = log2(wr) - qr / wr;
+        ip = ent_imp(wt, qt); il = ent_imp(wl, ql); ir = ent_imp(wr, qr);
       }
       g = ip - (wl / wt) * il - (wr / wt) * ir;
     }
@@ -397,7 +409,7 @@ __global__ __launch_bounds__(256) void tree_hist_split_kernel(
   // ---- split search: one wave per feature slot, one lane per bin ----
   // Per lane (= threshold bin) the class loop keeps only running sums — no per-class arrays
   // (which lived in scratch): gini needs sum c^2 of left / right / parent, entropy needs
-  // sum c log2 c (imp = log2 w - sum c log2 c / w), plus the weights.
+  // sum c log2 c (imp = (w log2 w - sum c log2 c) / w, ent_imp), plus the weights.
   double best_g = -INFINITY;
   int best_i = 0x7fffffff;
   const int nwaves = (int)(blockDim.x >> 6);
@@ -432,7 +444,7 @@ __global__ __launch_bounds__(256) void tree_hist_split_kernel(
           if (impurity == 0) {
             ip = 1.0 - qt / (wt * wt); il = 1.0 - ql / (wl * wl); ir = 1.0 - qr / (wr * wr);
           } else {
-            ip = log2(wt) - qt / wt; il = log2(wl) - ql / wl; ir = log2(wr) - qr / wr;
+            ip = ent_imp(wt, qt); il = ent_imp(wl, ql); ir = ent_imp(wr, qr);
           }
           g = ip - (wl / wt) * il - (wr / wt) * ir;
         }
@@ -477,7 +489,7 @@ __global__ __launch_bounds__(256) void tree_hist_split_kernel(
       if (impurity == 0) {
         ip = 1.0 - qt / (wt * wt); il = 1.0 - ql / (wl * wl); ir = 1.0 - qr / (wr * wr);
       } else {
-        ip = log2(wt) - qt / wt; il = log2(wl) - ql / wl; ir = log2(wr) - qr / wr;
+        ip = ent_imp(wt, qt); il = ent_imp(wl, ql); ir = ent_imp(wr, qr);
       }
       g = ip - (wl / wt) * il - (wr / wt) * ir;
     }
@@ -619,9 +631,12 @@ __global__ __launch_bounds__(256) void poisson_bootstrap_kernel(uint64_t seed, i
 // One pass per fit over the (tree, row) slots: bootstrap weight (Poisson(1) from Philox keyed by
 // (seed, global tree, global row), or 1) times an optional row weight -> W [T][N] fp32; node
 // ids [T][N] (0, or -1 where the weight is 0); root class counts written straight into
-// stats[t][0][K] (stats zeroed by the caller).  Labels outside [0, K) set *bad.  The counts are
+// stats[t][0][K] (stats zeroed by the caller).  Labels outside [0, K) set bit 0 of *bad.  The counts are
 // sums of integer-valued weights (< 2^24), so the LDS partials and the one global atomic per
-// (workgroup, class) are exact in any order: the result is deterministic.
+// (workgroup, class) are exact in any order: the result is deterministic.  That is the contract of
+// every level kernel (uint32 histogram adds, sibling subtraction, order-free merges), so a weight
+// that is not a non-negative integer below 2^24 (bootstrap x row weight) sets bit 1 of *bad; the
+// bits are OR-ed in atomically, so neither flag can overwrite the other.
 constexpr int INIT_ROWS = 2048;
 struct CdfTable {
   uint32_t thr[16];
@@ -649,13 +664,14 @@ __global__ __launch_bounds__(256) void tree_init_kernel(uint64_t seed, int tree0
       w = (float)k;
     }
     if (rw) w *= rw[(int64_t)t * n + r];
+    if (!(w >= 0.f) || w != rintf(w) || w >= 16777216.f) badl |= 2;  // (NaN fails w >= 0)
     W[(int64_t)t * n + r] = w;
     node_of[(int64_t)t * n + r] = w == 0.f ? -1 : 0;
     const int c = y[r];
-    if (c < 0 || c >= K) badl = 1;
+    if (c < 0 || c >= K) badl |= 1;
     else if (w != 0.f) atomicAdd(&cnt[c], w);
   }
-  if (badl) *bad = 1;
+  if (badl) atomicOr(bad, badl);
   __syncthreads();
   if (threadIdx.x < K && cnt[threadIdx.x] != 0.f) atomicAdd(stats + t * stats_tree_stride + threadIdx.x, cnt[threadIdx.x]);
 }
