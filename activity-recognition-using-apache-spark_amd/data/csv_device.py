@@ -44,6 +44,8 @@ from .table import Column, Table
 CHUNK = 4096  # bytes per workgroup of csv_count_newlines / csv_newline_pos
 INT32_MAX = 2 ** 31 - 1
 INT32_MIN = -(2 ** 31)
+INT64_MAX = 2 ** 63 - 1
+INT64_MIN = -(2 ** 63)
 F_NONEMPTY, F_INT, F_FLOAT, F_QUOTED, F_INEXACT = 1, 2, 4, 8, 16
 
 
@@ -56,7 +58,8 @@ class DeviceCsv:
     """Parsed CSV resident in HBM: per-column kind, fp64 values, hashes, flags, spans."""
 
     def __init__(self, raw: bytes, buf: torch.Tensor, names: List[str], kinds: List[str], vals: torch.Tensor,
-                 hashes: torch.Tensor, flags: torch.Tensor, fstart: torch.Tensor, flen: torch.Tensor):
+                 hashes: torch.Tensor, flags: torch.Tensor, fstart: torch.Tensor, flen: torch.Tensor,
+                 ints: Optional[Dict[int, torch.Tensor]] = None):
         self.raw = raw              # host copy of the bytes (string decoding of representatives only)
         self.buf = buf              # uint8 [nbytes] on the device
         self.names = names
@@ -66,6 +69,8 @@ class DeviceCsv:
         self.flags = flags          # uint8 [ncols, nrows]
         self.fstart = fstart        # int64 [ncols, nrows]
         self.flen = flen            # int32 [ncols, nrows]
+        # exact int64 plane [nrows] of every long column with a value fp64 cannot hold (|v| >= 2^53)
+        self.ints = ints or {}
 
     @property
     def nrows(self) -> int:
@@ -134,7 +139,9 @@ class DeviceCsv:
             f = self.flags[j]
             if kind in ("int", "long"):
                 miss = (f & F_FLOAT) == 0
-                v = torch.where(miss, torch.zeros_like(self.vals[j]), self.vals[j]).to(torch.int64)
+                v = self.ints.get(j)
+                if v is None:
+                    v = torch.where(miss, torch.zeros_like(self.vals[j]), self.vals[j]).to(torch.int64)
                 cols.append(DeviceColumn(name, kind, v, miss))
             elif kind == "double":
                 cols.append(DeviceColumn(name, "double", self.vals[j], (f & F_FLOAT) == 0))
@@ -173,7 +180,7 @@ class DeviceCsv:
             f = flags[j]
             if kind in ("int", "long"):
                 miss = (f & F_FLOAT) == 0
-                data = np.where(miss, 0, vals[j]).astype(np.int64)
+                data = self.ints[j].cpu().numpy() if j in self.ints else np.where(miss, 0, vals[j]).astype(np.int64)
                 cols.append(Column(name, kind, data, miss if miss.any() else None))
             elif kind == "double":
                 miss = (f & F_FLOAT) == 0
@@ -260,10 +267,34 @@ def parse_csv_device(raw: bytes, device="cuda", header: bool = True) -> DeviceCs
         mod.csv_parse_rows(buf.data_ptr(), starts.data_ptr(), ends.data_ptr(), nrows, ncols, vals.data_ptr(),
                            hashes.data_ptr(), flags.data_ptr(), fstart.data_ptr(), flen.data_ptr(),
                            _native.stream_ptr(dev))
-    kinds, n_inexact = _infer_kinds(vals, flags)
+    kinds, n_inexact, wide = _infer_kinds(vals, flags)
+    ints = {}
+    for j in wide:  # all-integer columns with |v| >= 2^53 somewhere: long or double is decided exactly
+        ints[j] = _exact_longs(raw, vals[j], flags[j], fstart[j], flen[j])
+        if ints[j] is None:
+            kinds[j] = "double"
+            del ints[j]
     if n_inexact:
         _fix_inexact(raw, vals, flags, fstart, flen)
-    return DeviceCsv(raw, buf, names, kinds, vals, hashes, flags, fstart, flen)
+    return DeviceCsv(raw, buf, names, kinds, vals, hashes, flags, fstart, flen, ints)
+
+
+def _exact_longs(raw: bytes, vals: torch.Tensor, flags: torch.Tensor, fstart: torch.Tensor, flen: torch.Tensor):
+    """int64 plane of an all-integer column whose fp64 plane is not exact: the fields with
+    |v| >= 2^53 (every integer below is exact in fp64) are re-parsed on the host with ``int`` —
+    rare, so few bytes move, like ``_fix_inexact``.  None when one of them does not fit int64
+    (the host parser's rule: such a column is a double)."""
+    isint = (flags & F_INT) != 0
+    wide = isint & (vals.abs() >= 2.0 ** 53)
+    idx = torch.nonzero(wide).squeeze(1)
+    st = fstart[idx].cpu().numpy()
+    ln = flen[idx].cpu().numpy()
+    exact = [int(raw[a:a + b].decode("ascii")) for a, b in zip(st, ln)]
+    if any(v > INT64_MAX or v < INT64_MIN for v in exact):
+        return None
+    plane = torch.where(isint & ~wide, vals, torch.zeros_like(vals)).to(torch.int64)
+    plane[idx] = torch.tensor(exact, dtype=torch.int64).to(vals.device)
+    return plane
 
 
 def _fix_inexact(raw: bytes, vals: torch.Tensor, flags: torch.Tensor, fstart: torch.Tensor, flen: torch.Tensor):
@@ -284,21 +315,22 @@ def _infer_kinds(vals: torch.Tensor, flags: torch.Tensor):
     any_ne = ne.any(1)
     non_float = (ne & ~isflt).any(1)
     non_int = (ne & ~isint).any(1)
-    big = vals.abs() > 9.2e18  # does not fit a Java long -> the column is a double
+    # an integer fp64 cannot hold exactly: whether it fits a Java long (else the column is a double)
+    # and its exact value are decided from its digits (_exact_longs), not from the rounded fp64
+    wide = (isint & (vals.abs() >= 2.0 ** 53)).any(1)
     fits32 = (vals <= INT32_MAX) & (vals >= INT32_MIN)
     overflow32 = (isint & ~fits32).any(1)
-    non_int = non_int | (isint & big).any(1)
     inexact = ((flags & F_INEXACT) != 0).sum(1)
-    votes = torch.stack([any_ne, non_float, non_int, overflow32, inexact.bool()], 1).cpu().numpy()
+    votes = torch.stack([any_ne, non_float, non_int, overflow32, inexact.bool(), wide], 1).cpu().numpy()
     kinds = []
-    for a, nf, ni, ov, _ in votes:
+    for a, nf, ni, ov, _, _ in votes:
         if not a or nf:
             kinds.append("string")
         elif not ni:
             kinds.append("long" if ov else "int")
         else:
             kinds.append("double")
-    return kinds, int(votes[:, 4].sum())
+    return kinds, int(votes[:, 4].sum()), [j for j, k in enumerate(kinds) if k == "long" and votes[j, 5]]
 
 
 def read_numeric_device(path: str, columns: List[str], device="cuda") -> Dict[str, torch.Tensor]:

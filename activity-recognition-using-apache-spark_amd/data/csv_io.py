@@ -17,53 +17,96 @@ test oracle.  For device-resident ETL of very large numeric CSVs see
 """
 from __future__ import annotations
 
-import csv
-import io
 import re
-from typing import List, Optional
+from typing import List, Optional, Tuple
 
 import numpy as np
 
 from .table import Column, Table
 
-_INT_RE = re.compile(r"^[+-]?\d+$")
-_FLOAT_RE = re.compile(r"^[+-]?(\d+\.?\d*([eE][+-]?\d+)?|\.\d+([eE][+-]?\d+)?|NaN|Infinity|-Infinity)$")
+_INT_RE = re.compile(r"[+-]?[0-9]+\Z")
+_FLOAT_RE = re.compile(r"[+-]?(?:(?:[0-9]+\.?[0-9]*|\.[0-9]+)(?:[eE][+-]?[0-9]+)?|NaN|Infinity)\Z")
 
 INT32_MAX = 2 ** 31 - 1
 INT32_MIN = -(2 ** 31)
+INT64_MAX = 2 ** 63 - 1
+INT64_MIN = -(2 ** 63)
 
 
-def _columns_from_fields(header: List[str], rows: List[List[str]]) -> Table:
-    ncol = len(header)
+def _split_line(line: str) -> List[Tuple[str, bool]]:
+    """Fields ``(text, quoted)`` of one line — ``split_line`` of ``csrc/host/csv_parser.cpp``: a field
+    that starts with ``"`` runs to its closing quote (``""`` escapes one), whatever follows up to the
+    next comma is dropped; a trailing comma adds one empty field."""
+    if '"' not in line:
+        return [(f, False) for f in line.split(",")]
+    out, i, e = [], 0, len(line)
+    while True:
+        if i < e and line[i] == '"':
+            j, buf = i + 1, []
+            while j < e:
+                if line[j] == '"':
+                    if j + 1 < e and line[j + 1] == '"':
+                        buf.append('"')
+                        j += 2
+                        continue
+                    break
+                buf.append(line[j])
+                j += 1
+            out.append(("".join(buf), True))
+            i = line.find(",", j + 1)
+        else:
+            k = line.find(",", i)
+            out.append((line[i:e if k < 0 else k], False))
+            i = k
+        if i < 0 or i >= e:
+            break
+        i += 1  # skip ','
+        if i == e:
+            out.append(("", False))
+            break
+    return out
+
+
+def _columns_from_fields(header: List[str], rows: List[List[Tuple[str, bool]]]) -> Table:
     cols = []
     for j, name in enumerate(header):
-        fields = [r[j] if j < len(r) else "" for r in rows]
-        nonempty = [f for f in fields if f != ""]
-        if nonempty and all(_INT_RE.match(f) for f in nonempty):
-            vals = np.array([int(f) if f != "" else 0 for f in fields], dtype=np.int64)
-            miss = np.array([f == "" for f in fields])
+        cells = [r[j] if j < len(r) else ("", False) for r in rows]
+        fields = [t for t, _ in cells]
+        present = [q or t != "" for t, q in cells]  # a quoted "" is a present, empty string
+        nonempty = [c for c, p in zip(cells, present) if p]
+        miss = np.array([not p for p in present], dtype=bool)
+        ints = None
+        if nonempty and all(not q and _INT_RE.match(t) for t, q in nonempty):
+            ints = [int(f) if p else 0 for f, p in zip(fields, present)]
+            if not all(INT64_MIN <= v <= INT64_MAX for v in ints):
+                ints = None  # an integer literal that does not fit a long: the column is a double
+        if ints is not None:
+            vals = np.array(ints, dtype=np.int64)
             kind = "int" if (vals.max() <= INT32_MAX and vals.min() >= INT32_MIN) else "long"
             cols.append(Column(name, kind, vals, miss if miss.any() else None))
-        elif nonempty and all(_FLOAT_RE.match(f) for f in nonempty):
-            vals = np.array([float(f) if f != "" else np.nan for f in fields], dtype=np.float64)
-            miss = np.array([f == "" for f in fields])
+        elif nonempty and all(not q and _FLOAT_RE.match(t) for t, q in nonempty):
+            vals = np.array([float(f) if p else np.nan for f, p in zip(fields, present)], dtype=np.float64)
             cols.append(Column(name, "double", vals, miss if miss.any() else None))
         else:
-            cols.append(Column(name, "string", np.array([f if f != "" else None for f in fields], dtype=object)))
-    del ncol
+            cols.append(Column(name, "string", np.array([f if p else None for f, p in zip(fields, present)],
+                                                        dtype=object)))
     return Table(cols)
 
 
 def parse_csv_text_python(text: str, header: bool = True) -> Table:
-    reader = csv.reader(io.StringIO(text))
-    rows = [r for r in reader if r]
+    """Line based like the native parser: every ``\\n`` ends a record (one ``\\r`` before it is
+    dropped), empty lines are skipped, a UTF-8 BOM is ignored."""
+    if text[:1] == "\ufeff":
+        text = text[1:]
+    lines = [ln[:-1] if ln.endswith("\r") else ln for ln in text.split("\n")]
+    rows = [_split_line(ln) for ln in lines if ln]
     if not rows:
         return Table()
     if header:
-        names, rows = rows[0], rows[1:]
+        names, rows = [t.strip(" ") for t, _ in rows[0]], rows[1:]
     else:
         names = [f"_c{i}" for i in range(len(rows[0]))]
-    return _columns_from_fields([n.strip() for n in names], rows)
+    return _columns_from_fields(names, rows)
 
 
 def _native():

@@ -20,8 +20,18 @@ import torch
 from ..ops import _native
 
 
+def value_counts_max_v(device) -> int:
+    """Largest vocabulary the ``har_value_counts`` kernel takes on ``device`` (its LDS counters)."""
+    with torch.cuda.device(device):
+        return int(_native.kernels().value_counts_max_v())
+
+
 def value_counts(codes: torch.Tensor, V: int) -> np.ndarray:
     codes = codes.to(torch.int64).contiguous()
+    if codes.is_cuda and V > value_counts_max_v(codes.device):
+        # more distinct values than a workgroup has LDS counters for: the device bincount
+        ok = (codes >= 0) & (codes < V)
+        return torch.bincount(codes[ok], minlength=V)[:V].cpu().numpy().astype(np.int64)
     if codes.is_cuda:
         out = torch.empty(V, dtype=torch.int64, device=codes.device)
         _native.kernels().value_counts(codes.data_ptr(), codes.numel(), V, out.data_ptr(), _native.stream_ptr())

@@ -317,6 +317,9 @@ class Table:
 
             cnt, mean, std, mn, mx = describe_device(dev_cols)
             for j, c in enumerate(dev_cols):
+                if cnt[j] == 0:  # no value at all: no mean, no extremes (as on the host below)
+                    out[c.name] = ["0", "NaN", "NaN", "null", "null"]
+                    continue
                 if c.kind in ("int", "long"):
                     lo, hi = str(int(mn[j])), str(int(mx[j]))
                 else:
@@ -332,7 +335,9 @@ class Table:
             cnt = len(x)
             mean = float(x.mean()) if cnt else float("nan")
             std = float(x.std(ddof=1)) if cnt > 1 else float("nan")
-            if c.kind in ("int", "long"):
+            if cnt == 0:  # (min / max of nothing: Spark prints null)
+                mn = mx = "null"
+            elif c.kind in ("int", "long"):
                 mn, mx = str(int(x.min())), str(int(x.max()))
             else:
                 mn, mx = java_double_str(float(x.min())), java_double_str(float(x.max()))

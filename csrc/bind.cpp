@@ -539,6 +539,7 @@ PYBIND11_MODULE(_har_native, m) {
     check(har_lbfgs_phase(&a, KP, phase, S(stream)), "lbfgs_phase");
   });
 
+  m.def("value_counts_max_v", &har_value_counts_max_v);
   m.def("value_counts", [](u codes, int64_t n, int V, u out, u stream) {
     check(har_value_counts(P<const int64_t>(codes), n, V, P<int64_t>(out), S(stream)), "value_counts");
   });

@@ -184,6 +184,7 @@ int har_bin_features(const float* X, int64_t n, int F, int ld, const float* thr,
                      uint8_t* bins, hipStream_t s);
 // counts of codes in [0, V) (V <= 32768; -1 / out-of-range ignored) into out[V] (zeroed here)
 int har_value_counts(const int64_t* codes, int64_t n, int V, int64_t* out, hipStream_t s);
+int har_value_counts_max_v();  // largest V the launcher accepts on the current device
 int har_confusion_matrix(const int32_t* label, const int32_t* pred, int64_t n, int K, int64_t* cm,
                          hipStream_t s);
 int har_regression_moments(const float* y, const float* yhat, int64_t n, double* out6, hipStream_t s);

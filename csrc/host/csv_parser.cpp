@@ -204,10 +204,13 @@ CsvResult parse_csv(const char* data, size_t size, bool header, int num_threads)
             if (isint) {
               errno = 0;
               long long v = std::strtoll(numbuf, nullptr, 10);
-              if (errno == ERANGE) votes[t][j] |= 1;  // does not fit long -> treat as double
+              const bool erange = errno == ERANGE;
+              if (erange) votes[t][j] |= 1;  // does not fit long -> treat as double
               if (v > 2147483647LL || v < -2147483648LL) votes[t][j] |= 4;
               res.ints[j][r] = v;
-              res.doubles[j][r] = (double)v;
+              // the value this field has in a double column is strtod of its text: v is clamped to
+              // LLONG_MAX / LLONG_MIN beyond int64, and "-0" is -0.0
+              res.doubles[j][r] = erange ? std::strtod(numbuf, nullptr) : (v == 0 && p[0] == '-') ? -0.0 : (double)v;
             } else {
               res.doubles[j][r] = std::strtod(numbuf, nullptr);
             }

@@ -99,7 +99,9 @@ __device__ void parse_field(const uint8_t* p, int len, bool quoted, double* val,
     bool eneg = false;
     if (i < len && (p[i] == '+' || p[i] == '-')) { eneg = p[i] == '-'; ++i; }
     int e = 0, ed = 0;
-    for (; i < len && p[i] >= '0' && p[i] <= '9'; ++i) { e = e * 10 + (p[i] - '0'); ++ed; }
+    // (saturating: a longer exponent would wrap the int and come back as an "exact" small one;
+    // at 100000 the field is far outside the fast path and takes the host strtod fix-up)
+    for (; i < len && p[i] >= '0' && p[i] <= '9'; ++i) { if (e < 100000) e = e * 10 + (p[i] - '0'); ++ed; }
     if (!ed) ok = false;
     exp10 += eneg ? -e : e;
   }

@@ -116,8 +116,17 @@ extern "C" int har_regression_moments(const float* y, const float* yhat, int64_t
   return 0;
 }
 
+// largest V of har_value_counts: one 32-bit LDS counter per value, within what a workgroup of the
+// current device may allocate (queried, not assumed) and at most 32768 (128 KB); <= 0: the query failed
+extern "C" int har_value_counts_max_v() {
+  int dev = 0, lds = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return 0;
+  if (hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess) return 0;
+  return std::min<int>(32768, lds / (int)sizeof(unsigned int));
+}
+
 extern "C" int har_value_counts(const int64_t* codes, int64_t n, int V, int64_t* out, hipStream_t s) {
-  if (V <= 0 || V > 32768 || n < 0) return -2;  // LDS counters: <= 128 KB
+  if (V <= 0 || V > har_value_counts_max_v() || n < 0) return -2;
   if (const hipError_t e = hipMemsetAsync(out, 0, sizeof(int64_t) * (size_t)V, s); e != hipSuccess) return (int)e;
   if (n == 0) return 0;
   const int blocks = (int)std::min<int64_t>(256, (n + 255) / 256);
