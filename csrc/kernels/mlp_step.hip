@@ -21,8 +21,10 @@
 //
 // mlp_bwd4 (S row slices x 4 h1-unit quadrants of 64 units; 64-row tiles, one barrier per tile;
 // producer waves 0-3 / consumer waves 4-7, see the kernel's comment):
-//   producers: dact2 tile i+1 (copied, loaded two tiles ahead) -> LDS | X tile i+2 -> LDS | h1 tile
-//              i+1 recomputed from X | (c) dW0 += dact1^T . X and db0 of tile i-1
+//   producers: dact2 tile i+1 and X tile i+2 -> LDS by LDS-DMA (global_load_lds_dwordx4: no VGPR
+//              destination, no LDS store; images in mlp_bwd_img.h), issued at the top of the iteration and
+//              waited for right before its barrier | h1 tile i+1 recomputed from X | (c) dW0 += dact1^T . X
+//              and db0 of tile i-1
 //   consumers: (a) dact1^T = W1^T[u] . dact2^T, relu'(h1) | (b) dW1 += h1^T . dact2 | db1 = sum_rows
 //              dact2 (a ones-row MFMA, 64 j per quadrant)
 // One deterministic partial per (slice, quadrant), laid out like the flat parameter buffer.
@@ -32,6 +34,7 @@
 
 #include "common.h"
 #include "mlp_frag.h"
+#include "mlp_bwd_img.h"
 #include "../har_kernels.h"
 
 using namespace mlpf;
@@ -540,23 +543,40 @@ __global__ __launch_bounds__(512) void mlp_fwd3_kernel(
 // ------------------------------------------------------------------------------------------------
 constexpr int BQ = 4, BQU = HH / BQ;  // 64 h1 units per workgroup
 constexpr int BRT = 64;               // rows per pipeline tile
-constexpr int BDP = HH + 16;          // dact2 tile pitch: 136 dwords (8 mod 64)
 constexpr int BUP = BQU + 16;         // h1 / dact1 quadrant tile pitch: 40 dwords; 8-byte chunks
                                       // swizzled by row (frag_rows_q)
+static_assert(bwdimg::ROWS == BRT && bwdimg::H == HH, "mlp_bwd_img.h describes this kernel's tiles");
 
+// dact2 and X tiles: the LDS-DMA images of mlp_bwd_img.h (dact2 [32][2][256] at pitch 528, X unpadded
+// with XOR-swizzled chunks); h1 / dact1 quadrant tiles: written by MFMA epilogues, pitch BUP
 template <int K0> struct Bwd4Lds {
-  static constexpr int XP = K0 + 16;
-  static constexpr int NXB = 4;  // X tile buffers (staged two tiles ahead; read by h1 / (c) two tiles apart)
+  static constexpr int NXB = 4;  // X tile buffers (filled two tiles ahead; read by h1 / (c) two tiles apart)
   static_assert((NXB & (NXB - 1)) == 0, "buffer indices are taken with & (NXB - 1)");
-  static constexpr int DSM = BRT * BDP, HS = BRT * BUP, XS = BRT * XP;
+  static constexpr int DSM = bwdimg::D2_ELEMS, HS = BRT * BUP, XS = bwdimg::x_elems(K0);
   static constexpr size_t bytes = (size_t)(2 * DSM + 2 * HS + 2 * HS + NXB * XS) * sizeof(bf16_t);
+  static_assert(bytes <= 160 * 1024, "LDS budget");
   static_assert((size_t)NCLS * HH + HH * BQU <= (size_t)2 * DSM, "the prologue images fit the dact2 buffers");
+  static_assert(HH * BQU <= DSM, "the W1^T quadrant image fits dact2 buffer 1");
 };
+
+// one LDS-DMA wave-instruction (global_load_lds_dwordx4): lane l's 16 bytes at `src` (per lane) land at
+// `dst` + 16 l (dst wave-uniform).  No VGPR destination, no LDS store; counted by vmcnt.
+__device__ __forceinline__ void dma16(const bf16_t* src, bf16_t* dst) {
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                   (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+}
+// MFMA operand fragment from two transposing 8-byte reads at element offsets lo / hi of `img`
+__device__ __forceinline__ bf16x8_t frag_tr2(const bf16_t* img, int lo_off, int hi_off) {
+  const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(img + lo_off));
+  const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(img + hi_off));
+  const s16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+  return __builtin_bit_cast(bf16x8_t, v);
+}
 
 // ------------------------------------------------------------------------------------------------
 // backward, wave-specialized (mlp_bwd4): the 8 waves split by role.  Waves 0..3 PRODUCE the next
-// tile's operands (the dact2 tile copied from the forward's dact2 rows, the X tile staging and the h1
-// recompute: loads, LDS stores and a few small MFMAs) and take the (c) dW0 / db0 products of the
+// tile's operands (the dact2 tile of the forward's dact2 rows and the X tile, both filled by LDS-DMA,
+// and the h1 recompute: a few small MFMAs) and take the (c) dW0 / db0 products of the
 // previous tile; waves 4..7 CONSUME the current tile (the (a) dact1, (b) dW1, db1 products: MFMA with
 // LDS fragment reads).  Each SIMD hosts one
 // producer and one consumer, so the producer's load / LDS-store stream issues beside the consumer's
@@ -565,8 +585,14 @@ template <int K0> struct Bwd4Lds {
 //   consumer c: (a) unit blocks 2 (c & 1) .. + 1 x row blocks 2 (c >> 1) .. + 1 (W1^T fragments in
 //               registers, dact2 rows from LDS); (b) all 4 unit blocks x j blocks 4c .. 4c + 3
 //               (64 dW1 accumulators); db1 of j block 4q + c
-//   producer p: dact2 / X staging (8 / 1-2 16-byte pieces per thread, loaded two tiles ahead); h1
-//               unit block p x all 4 row blocks; (c) unit block p x every input block, db0 of unit block p
+//   producer p: dact2 / X fills (8 / 1-2 LDS-DMA wave-instructions of 1 KiB per tile); h1 unit block
+//               p x all 4 row blocks; (c) unit block p x every input block, db0 of unit block p
+// Staging through registers (two sets of 8 uint4 loaded two tiles ahead + 10 ds_write_b128 per lane and
+// tile) cost the producers ~1.3k of a 2.6k-cycle tile — the VGPR -> LDS store path, not the LDS array
+// — and made them the critical role; with the fills the backward runs 29.1 -> 27.1 us, the step
+// 0.0522-0.0528 -> 0.0503-0.0508 ms over 500 steps, bitwise the same gradients
+// (profiles/r11/mlp_bwd_dma_ab.md).  Left on the table: before an LDS store (the h1 tile) and before
+// (c)'s transposing reads hipcc waits vmcnt(0) for the fills in flight, in the middle of the iteration.
 // The forward computes dact2 = (dz . Wout) * relu'(h2) beside its dWout stage (16x16x16 MFMAs on data
 // it holds anyway) and writes it in this kernel's LDS tile order: the 4 quadrant workgroups of a row
 // slice then copy the same rows (one HBM read, three L2 / MALL hits) instead of each rebuilding them
@@ -581,16 +607,15 @@ __global__ __launch_bounds__(512) void mlp_bwd4_kernel(
     const float* __restrict__ fslab, int fslab_w, int nfwd, float* __restrict__ gwo, float* __restrict__ gbo,
     uint64_t* __restrict__ stamps, int nt_slab) {
   using L = Bwd4Lds<K0>;
-  constexpr int NXB = L::NXB, KC = HH / 32, XP = L::XP, NFW = K0 / 32, NFB = K0 / 16;
-  constexpr int XV = BRT * K0 / 8;  // 16-byte vectors of an X tile (512 / 256)
-  constexpr int XPT = XV / 256;     // per producer thread (2 / 1)
-  constexpr int DV = BRT * HH / 8 / 256;  // 16-byte dact2 pieces per producer thread and tile (8)
+  constexpr int NXB = L::NXB, KC = HH / 32, NFW = K0 / 32, NFB = K0 / 16;
+  constexpr int DPW = bwdimg::D2_PIECES / 4;    // dact2 LDS-DMA pieces per producer wave and tile (8)
+  constexpr int XPW = bwdimg::x_pieces(K0) / 4;  // X pieces per producer wave and tile (2 / 1)
   if (tick && blockIdx.x == 0 && threadIdx.x == 0) *tick += 1;
   extern __shared__ __attribute__((aligned(16))) bf16_t lds[];
-  bf16_t* const dsm0 = lds;                // [2][64][BDP] dact2 tiles
+  bf16_t* const dsm0 = lds;                // [2] dact2 tiles (mlp_bwd_img.h)
   bf16_t* const hs0 = dsm0 + 2 * L::DSM;   // [2][64][BUP] h1 quadrant tiles
   bf16_t* const d1s0 = hs0 + 2 * L::HS;    // [2][64][BUP] dact1 quadrant tiles
-  bf16_t* const xs0 = d1s0 + 2 * L::HS;    // [NXB][64][XP] X tiles
+  bf16_t* const xs0 = d1s0 + 2 * L::HS;    // [NXB] X tiles (mlp_bwd_img.h)
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // scalar: the role branches are s_cbranch
   const int c16 = lane & 15, g = lane >> 4;
@@ -603,18 +628,19 @@ __global__ __launch_bounds__(512) void mlp_bwd4_kernel(
   const int ntiles = B / BRT, per = (ntiles + S - 1) / S;
   const int t0 = slice * per, n = max(0, min(ntiles, t0 + per) - t0);
 
-  // ---- prologue (all waves): W1^T quadrant fragments into LDS, the forward's dWout slabs ----
+  // ---- prologue (all waves): the W1^T quadrant fragments into LDS — into dact2 buffer 1, which no
+  // DMA writes before iteration 0 of the tile loop, so the producers' fills of dact2 tile 0 (buffer 0)
+  // and X tiles 0 / 1 go out first and land beside it ----
   const bf16_t* const W0f = Wf;
   const bf16_t* const W1tq = Wf + HH * K0 + HH * HH + (size_t)(4 * q) * KC * 512;
-  bf16_t* const w1q = lds + NCLS * HH;
-  {
+  bf16_t* const w1q = dsm0 + L::DSM;
+  auto stage_w1t = [&]() __attribute__((always_inline)) {
     uint4 st[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) st[i] = *reinterpret_cast<const uint4*>(W1tq + (size_t)(i * 8 + wave) * 512 + lane * 8);
 #pragma unroll
     for (int i = 0; i < 4; ++i) *reinterpret_cast<uint4*>(w1q + (i * 8 + wave) * 512 + lane * 8) = st[i];
-  }
-  __syncthreads();
+  };
   // a row of ones (A operand: row 0) / a column of ones (B operand: column 0): the same registers
   const bf16x8_t ones = __builtin_bit_cast(bf16x8_t, c16 == 0 ? s16x8_t{0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80,
                                                                         0x3f80, 0x3f80, 0x3f80}
@@ -623,74 +649,40 @@ __global__ __launch_bounds__(512) void mlp_bwd4_kernel(
 
   if (prod) {
     // ================================ producer ================================
-    const int ptid = tid;  // 0..255
-    static_assert(XPT == 1 || XPT == 2, "one or two X vectors per producer thread");
-    static_assert(DV == 8, "8 dact2 pieces per producer thread");
-    // dact2 piece i of a tile: row (ptid >> 5) + 8 i, 16-byte chunk ptid & 31 (a wave-instruction reads
-    // two whole 512-byte rows); LDS rows BDP apart (the forward wrote the chunk swizzle already)
+    static_assert(DPW == 8 && (XPW == 1 || XPW == 2), "dact2 / X pieces per producer wave");
+    // LDS-DMA fills (mlp_bwd_img.h): producer wave pw issues dact2 pieces 8 pw .. 8 pw + 7 (rows
+    // 8 pw .. + 7 and 32 + 8 pw .. + 7: two contiguous 4 KiB of the forward's rows) and X pieces pw
+    // (+ 4), 16 bytes per lane each; the images' swizzles are in WHICH chunk a lane fetches.
+    // Tile indices past the batch's last tile are clamped to it (filled, never consumed): every source
+    // address stays inside dact2 / X, also for a slice without tiles.
     // (lane offsets 32-bit, tile bases wave-uniform: the loads take the SGPR-base form)
-    const uint32_t d2src = (uint32_t)((ptid >> 5) * HH + (ptid & 31) * 8);  // (unsigned: zero-extended offsets)
-    const int d2dst = (ptid >> 5) * BDP + (ptid & 31) * 8;
-    // (macros, not lambdas: a lambda-captured register array is kept in scratch)
-    // two register sets of dact2 pieces: the tile staged at iteration i was loaded at iteration i - 2
-    // (one iteration ahead left ~700 cycles of the refill still in flight at its use, profiles/r5)
-    uint4 da0, da1, da2, da3, da4, da5, da6, da7, db0_, db1_, db2_, db3_, db4_, db5_, db6_, db7_;
-    uint4 xr0, xr1, xq0, xq1;  // xq: X tile t0 + 1, loaded with tile t0
-#define HAR_B4_LOAD_D(t, ...) HAR_B4_LOAD_D_I(t, __VA_ARGS__)
-#define HAR_B4_LOAD_D_I(t, r0_, r1_, r2_, r3_, r4_, r5_, r6_, r7_)            \
-  {                                                                           \
-    const int tt_ = min(t, tlast);                                            \
-    const bf16_t* dp_ = dact2 + (size_t)tt_ * (BRT * HH);                     \
-    r0_ = *reinterpret_cast<const uint4*>(dp_ + (d2src + 0 * 8 * HH));        \
-    r1_ = *reinterpret_cast<const uint4*>(dp_ + (d2src + 1 * 8 * HH));        \
-    r2_ = *reinterpret_cast<const uint4*>(dp_ + (d2src + 2 * 8 * HH));        \
-    r3_ = *reinterpret_cast<const uint4*>(dp_ + (d2src + 3 * 8 * HH));        \
-    r4_ = *reinterpret_cast<const uint4*>(dp_ + (d2src + 4 * 8 * HH));        \
-    r5_ = *reinterpret_cast<const uint4*>(dp_ + (d2src + 5 * 8 * HH));        \
-    r6_ = *reinterpret_cast<const uint4*>(dp_ + (d2src + 6 * 8 * HH));        \
-    r7_ = *reinterpret_cast<const uint4*>(dp_ + (d2src + 7 * 8 * HH));        \
-  }
-#define HAR_B4_STAGE_D(buf, ...) HAR_B4_STAGE_D_I(buf, __VA_ARGS__)
-#define HAR_B4_STAGE_D_I(buf, r0_, r1_, r2_, r3_, r4_, r5_, r6_, r7_)         \
-  {                                                                           \
-    bf16_t* d_ = dsm0 + (buf) * L::DSM + d2dst;                               \
-    *reinterpret_cast<uint4*>(d_ + 0 * 8 * BDP) = r0_;                        \
-    *reinterpret_cast<uint4*>(d_ + 1 * 8 * BDP) = r1_;                        \
-    *reinterpret_cast<uint4*>(d_ + 2 * 8 * BDP) = r2_;                        \
-    *reinterpret_cast<uint4*>(d_ + 3 * 8 * BDP) = r3_;                        \
-    *reinterpret_cast<uint4*>(d_ + 4 * 8 * BDP) = r4_;                        \
-    *reinterpret_cast<uint4*>(d_ + 5 * 8 * BDP) = r5_;                        \
-    *reinterpret_cast<uint4*>(d_ + 6 * 8 * BDP) = r6_;                        \
-    *reinterpret_cast<uint4*>(d_ + 7 * 8 * BDP) = r7_;                        \
-  }
-#define HAR_DA da0, da1, da2, da3, da4, da5, da6, da7
-#define HAR_DB db0_, db1_, db2_, db3_, db4_, db5_, db6_, db7_
-#define HAR_B4_LOAD_XR(t, xa_, xb2_)                                                          \
-  {                                                                                           \
-    const int tt_ = min(t, tlast);                                                            \
-    const bf16_t* xp_ = X + (size_t)tt_ * (XV * 8);                                           \
-    xa_ = *reinterpret_cast<const uint4*>(xp_ + (uint32_t)(ptid * 8));                        \
-    if constexpr (XPT == 2) xb2_ = *reinterpret_cast<const uint4*>(xp_ + (uint32_t)((ptid + 256) * 8)); \
-  }
-#define HAR_B4_STAGE_XR(i, xa_, xb2_)                                                                      \
-  {                                                                                                        \
-    bf16_t* xb_ = xs0 + ((i) & (NXB - 1)) * L::XS;                                                         \
-    *reinterpret_cast<uint4*>(xb_ + (ptid / (K0 / 8)) * XP + (ptid % (K0 / 8)) * 8) = xa_;                 \
-    if constexpr (XPT == 2)                                                                                \
-      *reinterpret_cast<uint4*>(xb_ + ((ptid + 256) / (K0 / 8)) * XP + ((ptid + 256) % (K0 / 8)) * 8) = xb2_; \
-  }
-#define HAR_B4_LOAD_X(t) HAR_B4_LOAD_XR(t, xr0, xr1)
-#define HAR_B4_STAGE_X(i) HAR_B4_STAGE_XR(i, xr0, xr1)
-    // the first tiles' loads go out before anything else of the prologue (W0 fragments, the dWout
-    // slabs): dact2 tile 0 and X tiles 0 / 1 land in one round trip, staged after the barrier below
-    HAR_B4_LOAD_D(t0, HAR_DA)
-    HAR_B4_LOAD_X(t0)
-    HAR_B4_LOAD_XR(t0 + 1, xq0, xq1)
+    auto dma_d = [&](int t, int buf) __attribute__((always_inline)) {
+      const bf16_t* dp = dact2 + (size_t)min(t, tlast) * (BRT * HH);
+      bf16_t* dd = dsm0 + buf * L::DSM;
+#pragma unroll
+      for (int k = 0; k < DPW; ++k)
+        dma16(dp + (uint32_t)bwdimg::d2_src(DPW * pw + k, lane), dd + bwdimg::d2_dst(DPW * pw + k));
+    };
+    auto dma_x = [&](int t, int i) __attribute__((always_inline)) {
+      const bf16_t* xp = X + (size_t)min(t, tlast) * (BRT * K0);
+      bf16_t* xd = xs0 + (i & (NXB - 1)) * L::XS;
+#pragma unroll
+      for (int k = 0; k < XPW; ++k)
+        dma16(xp + (uint32_t)bwdimg::x_src(K0, pw + 4 * k, lane), xd + bwdimg::x_dst(pw + 4 * k));
+    };
+    // the first tiles' fills go out before anything else of the prologue: dact2 tile 0 and X tiles
+    // 0 / 1 land in one round trip, beside the W1^T image
+    dma_d(t0, 0);
+    dma_x(t0, 0);
+    dma_x(t0 + 1, 1);
     bf16x8_t w0q[NFW];
 #pragma unroll
     for (int kc = 0; kc < NFW; ++kc)
       w0q[kc] = *reinterpret_cast<const bf16x8_t*>(W0f + (size_t)((4 * q + pw) * NFW + kc) * 512 + frag_lane_off(lane));
     const float4 b0q = *reinterpret_cast<const float4*>(b0 + qu0 + 16 * pw + 4 * g);
+    stage_w1t();
+    __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0): this wave's fills of dact2 tile 0 and X tiles 0 / 1 have landed
+    __syncthreads();  // P1: the W1^T image, dact2 tile 0 and X tiles 0 / 1 are in LDS, visible to every wave
     constexpr int WO4 = NCLS * HH / 4, NC4 = WO4 + NCLS / 4;
     f32x4_t px[4];
     auto wo_load = [&](int c4) __attribute__((always_inline)) {
@@ -700,6 +692,8 @@ __global__ __launch_bounds__(512) void mlp_bwd4_kernel(
         px[r] = lane + 64 * r < nfwd ? *reinterpret_cast<const f32x4_t*>(src + (size_t)(lane + 64 * r) * fslab_w)
                                      : f32x4_t{0.f, 0.f, 0.f, 0.f};
     };
+    // (after P1: issued before it, the barrier's vmcnt(0) would wait for this gather too; first used
+    // after the last tile)
     if (fslab && 4 * b + pw < NC4) wo_load(4 * b + pw);
     if constexpr (STAMP) __builtin_amdgcn_s_waitcnt(0x0f70);
     HAR_STAMP(8, 1)
@@ -715,7 +709,7 @@ __global__ __launch_bounds__(512) void mlp_bwd4_kernel(
       for (int rr = 0; rr < 4; ++rr)
 #pragma unroll
         for (int kc = 0; kc < NFW; ++kc)
-          xf[rr][kc] = *reinterpret_cast<const bf16x8_t*>(xs + (16 * rr + c16) * XP + kc * 32 + 8 * g);
+          xf[rr][kc] = *reinterpret_cast<const bf16x8_t*>(xs + bwdimg::x_h1_off(K0, 16 * rr + c16, kc, g));
       __builtin_amdgcn_sched_barrier(0);
       f32x4_t a[4];
 #pragma unroll
@@ -742,65 +736,37 @@ __global__ __launch_bounds__(512) void mlp_bwd4_kernel(
       for (int ks = 0; ks < 2; ++ks) {
         const bf16x8_t A = frag_rows_q(d1s + 32 * ks * BUP, BUP, 16 * pw, lane);
 #pragma unroll
-        for (int f = 0; f < NFB; ++f) acc0[f] = mma32(A, frag_rows(xs + 32 * ks * XP, XP, 16 * f, lane), acc0[f]);
+        for (int f = 0; f < NFB; ++f)  // (the permuted k order of frag_rows: rows 4g .. + 3, 16 + 4g .. + 3 of the step)
+          acc0[f] = mma32(A, frag_tr2(xs, bwdimg::x_c_off(K0, ks, f, lane, 0), bwdimg::x_c_off(K0, ks, f, lane, 1)), acc0[f]);
         accd0 = mma32(A, ones, accd0);
       }
     };
-    // invariant at the top of iteration i: the dact2 set of i's parity (A even, B odd) holds tile i+1,
-    // the other set tile i+2; xr = X tile i+2 (loaded)
-    __syncthreads();  // the prologue images are read: the tile buffers may be written
-    HAR_B4_STAGE_D(0, HAR_DA)
-    HAR_B4_STAGE_X(0)
-    HAR_B4_STAGE_XR(1, xq0, xq1)
-    HAR_B4_LOAD_D(t0 + 1, HAR_DA)
-    HAR_B4_LOAD_D(t0 + 2, HAR_DB)
-    HAR_B4_LOAD_X(t0 + 2)
-    __builtin_amdgcn_sched_barrier(0);
-    __syncthreads();  // dact2 tile 0, X tiles 0 and 1 are in LDS
-    tile_h1(0);
-    __syncthreads();  // h1 tile 0 complete
-#define HAR_B4_ITER(i, ...)                                                                             \
-  {                                                                                                     \
-    if ((i) < 24) HAR_STAMP(8, 2 + (i))                                                                 \
-    if constexpr (STAMP) { /* (stamped build only: how long the dact2 refill is still in flight) */    \
-      if ((i) == 4) {                                                                                   \
-        __builtin_amdgcn_s_waitcnt(0x0f70 | (8 + XPT));                                                 \
-        HAR_STAMP(8, 32)                                                                                \
-      }                                                                                                 \
-    }                                                                                                   \
-    HAR_B4_STAGE_D(((i) + 1) & 1, __VA_ARGS__) /* waits for the dact2 loads issued two iterations ago */ \
-    if ((i) == 4) HAR_STAMP(8, 26)                                                                      \
-    HAR_B4_STAGE_X((i) + 2)                                                                             \
-    /* the refills may not be hoisted above the last reads of the registers they overwrite: a hoisted  \
-       load gets fresh registers, and the loop-carried copy back then waits out its whole latency */   \
-    __builtin_amdgcn_sched_barrier(0);                                                                  \
-    HAR_B4_LOAD_D(t0 + (i) + 3, __VA_ARGS__)                                                            \
-    HAR_B4_LOAD_X(t0 + (i) + 3)                                                                         \
-    __builtin_amdgcn_sched_barrier(0); /* the refills are issued before the h1 recompute */           \
-    if ((i) == 4) HAR_STAMP(8, 27)                                                                      \
-    tile_h1((i) + 1); /* X tile i+1 has been in LDS since the last barrier */                         \
-    if ((i) == 4) HAR_STAMP(8, 28)                                                                      \
-    if ((i) > 0) tile_c((i) - 1); /* dact1 i-1 completed at the last barrier; X i-1 is still staged */  \
-    if ((i) == 4) HAR_STAMP(8, 33)                                                                      \
-    __syncthreads(); /* dact2 i+1 / X i+2 staged, h1 i+1 complete; the consumers finished tile i */    \
-  }
-    int i = 0;
-    for (; i + 1 < n; i += 2) {
-      HAR_B4_ITER(i, HAR_DA)
-      HAR_B4_ITER(i + 1, HAR_DB)
-    }
-    if (i < n) HAR_B4_ITER(i, HAR_DA)
-#undef HAR_B4_ITER
-#undef HAR_B4_STAGE_D
-#undef HAR_B4_STAGE_D_I
-#undef HAR_DA
-#undef HAR_DB
-#undef HAR_B4_LOAD_D
-#undef HAR_B4_LOAD_D_I
-#undef HAR_B4_LOAD_X
-#undef HAR_B4_STAGE_X
-#undef HAR_B4_LOAD_XR
-#undef HAR_B4_STAGE_XR
+    tile_h1(0);  // X tile 0: visible since P1
+    __syncthreads();  // P2: h1 tile 0 complete; the consumers have read the W1^T image (dact2 buffer 1 is free)
+    // Iteration i: the fills of dact2 tile i+1 (buffer (i+1) & 1, which the consumers released at the
+    // barrier ending iteration i-1 — at P2 for i = 0) and of X tile i+2 (slot (i+2) & 3, last read by (c)
+    // of tile i-2 in iteration i-1) are issued first and have the whole iteration to land; every
+    // producer wave waits vmcnt(0) for its own pieces before the barrier that ends the iteration.
+    // That barrier makes dact2 tile i+1 visible to the consumers' (a) / (b) / db1 reads of iteration
+    // i+1, and X tile i+2 visible to the producers' h1 recompute of iteration i+1 and (c) of iteration
+    // i+3: every read is one barrier after the wait that retired the fill.
+    auto piter = [&](int i) __attribute__((always_inline)) {
+      if (i < 24) HAR_STAMP(8, 2 + i)
+      dma_d(t0 + i + 1, (i + 1) & 1);
+      if (i == 4) HAR_STAMP(8, 26)
+      dma_x(t0 + i + 2, i + 2);
+      __builtin_amdgcn_sched_barrier(0);  // the fills are issued before the h1 recompute
+      if (i == 4) HAR_STAMP(8, 27)
+      tile_h1(i + 1);  // X tile i+1 has been in LDS since the last barrier
+      if (i == 4) HAR_STAMP(8, 28)
+      if (i > 0) tile_c(i - 1);  // dact1 i-1 completed at the last barrier; X i-1 is still in its slot
+      if (i == 4) HAR_STAMP(8, 33)
+      __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0): this wave's pieces of dact2 i+1 / X i+2 have landed
+      if (i == 4) HAR_STAMP(8, 32)  // (stamped build: 33 -> 32 is how long the fills were still in flight)
+      __syncthreads();  // dact2 i+1 / X i+2 in LDS, h1 i+1 complete; the consumers finished tile i
+    };
+    for (int i = 0; i < n; ++i) piter(i);
     HAR_STAMP(8, 34)
     if (n > 0) tile_c(n - 1);
     float* w0o = gw0 + (size_t)slice * slab_stride;
@@ -837,6 +803,8 @@ __global__ __launch_bounds__(512) void mlp_bwd4_kernel(
   } else {
     // ================================ consumer ================================
     const int ua0 = 2 * (pw & 1), ra0 = 2 * (pw >> 1);
+    stage_w1t();
+    __syncthreads();  // P1 (paired with the producers'): the W1^T image is complete
     bf16x8_t w1t[2][KC];  // (a) A fragments: A[u][k = j] = W1[32 kc + 8g + i][qu0 + 16 (ua0 + e) + c16]
 #pragma unroll
     for (int e = 0; e < 2; ++e)
@@ -845,9 +813,6 @@ __global__ __launch_bounds__(512) void mlp_bwd4_kernel(
         w1t[e][kc] = *reinterpret_cast<const bf16x8_t*>(w1q + ((ua0 + e) * KC + kc) * 512 + frag_lane_off(lane));
     if constexpr (STAMP) __builtin_amdgcn_s_waitcnt(0x0f70);
     HAR_STAMP(8, 1)
-    // (paired with the producers' "prologue images are read" barrier: the W1^T image is read above,
-    // the producers then overwrite it with dact2 tile 0)
-    __syncthreads();
     f32x4_t acc1[4][4], accb = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int j = 0; j < 4; ++j)
@@ -868,7 +833,6 @@ __global__ __launch_bounds__(512) void mlp_bwd4_kernel(
       const bf16_t* hs = hs0 + par * L::HS;
       bf16_t* d1s = d1s0 + par * L::HS;
       constexpr int PD = 3;  // prefetch distance (k chunks)
-      const int swz = 8 * ((c16 >> 2) & 1);
       // (an isolated scheduling region whose first group is the hm reads + the PD chunks ahead: without
       // it the scheduler put each chunk's own reads into the per-chunk read groups, right before their
       // MFMAs — no prefetch at all, profiles/r5)
@@ -884,7 +848,7 @@ __global__ __launch_bounds__(512) void mlp_bwd4_kernel(
       for (int kc = 0; kc < PD; ++kc)
 #pragma unroll
         for (int rr = 0; rr < 2; ++rr)
-          bv[rr][kc] = *reinterpret_cast<const bf16x8_t*>(dsm + (16 * (ra0 + rr) + c16) * BDP + ((kc * 32 + 8 * g) ^ swz));
+          bv[rr][kc] = *reinterpret_cast<const bf16x8_t*>(dsm + bwdimg::d2_a_off(ra0 + rr, c16, kc, g));
       __builtin_amdgcn_sched_group_barrier(0x100, 2 * PD + 4, 0);
       f32x4_t acc[2][2];
 #pragma unroll
@@ -897,7 +861,7 @@ __global__ __launch_bounds__(512) void mlp_bwd4_kernel(
 #pragma unroll
           for (int rr = 0; rr < 2; ++rr)
             bv[rr][kc + PD] =
-                *reinterpret_cast<const bf16x8_t*>(dsm + (16 * (ra0 + rr) + c16) * BDP + (((kc + PD) * 32 + 8 * g) ^ swz));
+                *reinterpret_cast<const bf16x8_t*>(dsm + bwdimg::d2_a_off(ra0 + rr, c16, kc + PD, g));
           __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);  // the 2 LDS reads of chunk kc + PD
         }
 #pragma unroll
@@ -928,16 +892,17 @@ __global__ __launch_bounds__(512) void mlp_bwd4_kernel(
         for (int u = 0; u < 4; ++u) hb[u] = frag_rows_q(hs + 32 * ks * BUP, BUP, 16 * u, lane);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const bf16x8_t da = frag_rows_sw(dsm + 32 * ks * BDP, BDP, 16 * (4 * pw + j), lane);
+          const bf16x8_t da = frag_tr2(dsm, bwdimg::d2_b_off(ks, 16 * (4 * pw + j), lane, 0), bwdimg::d2_b_off(ks, 16 * (4 * pw + j), lane, 1));
 #pragma unroll
           for (int u = 0; u < 4; ++u) acc1[j][u] = mma32(hb[u], da, acc1[j][u]);  // C[u][j]
         }
-        accb = mma32(ones, frag_rows_sw(dsm + 32 * ks * BDP, BDP, 16 * (4 * q + pw), lane), accb);
+        accb = mma32(ones, frag_tr2(dsm, bwdimg::d2_b_off(ks, 16 * (4 * q + pw), lane, 0), bwdimg::d2_b_off(ks, 16 * (4 * q + pw), lane, 1)), accb);
       }
     };
     __builtin_amdgcn_s_setprio(1);  // the consumers' MFMA stream is the critical path of a tile
-    __syncthreads();  // (paired with the producers' barrier: dact2 0, X 0 / 1 staged)
-    __syncthreads();  // (paired: h1 tile 0 complete)
+    // P2 (paired: h1 tile 0 complete).  The W1^T image is read above (__syncthreads waits for this
+    // wave's LDS reads): the producers then fill dact2 tile 1 over it
+    __syncthreads();
     auto citer = [&](int i, auto parc) __attribute__((always_inline)) {
       constexpr int par = decltype(parc)::value;
       if (i < 24) HAR_STAMP(8, 2 + i)

@@ -105,10 +105,17 @@ def stamps(B=65536):
             for nm, v in sub:
                 print(f"  {nm:28s} median {np.median(v):9.0f}  max {v.max():9.0f} cycles")
         if k == 1 and bwd4 and producer and (s[:, 26] > 0).all():  # mlp_bwd4 producer phases of tile 4
-            sub = [("  tile 4: dact2 refill wait", s[:, 32] - s[:, 6]),
-                   ("  tile 4: dact2 (tile 5) -> LDS", s[:, 26] - s[:, 32]), ("  tile 4: X stage + refills", s[:, 27] - s[:, 26]),
+            # LDS-DMA staging: the fills are issued first (slots 26 / 27) and waited for (vmcnt(0), slot 32)
+            # after (c), right before the tile barrier
+            sub = [("  tile 4: dact2 (tile 5) fills issued", s[:, 26] - s[:, 6]),
+                   ("  tile 4: X (tile 6) fills issued", s[:, 27] - s[:, 26]),
                    ("  tile 4: h1 recompute (tile 5)", s[:, 28] - s[:, 27]), ("  tile 4: (c) dW0 + db0 (tile 3)", s[:, 33] - s[:, 28]),
-                   ("  tile 4: barrier", s[:, 7] - s[:, 33])]
+                   ("  tile 4: fills still in flight", s[:, 32] - s[:, 33]), ("  tile 4: barrier", s[:, 7] - s[:, 32])]
+            if np.median(s[:, 32]) < np.median(s[:, 26]):  # a build with register staging (A/B against an older library)
+                sub = [("  tile 4: dact2 refill wait", s[:, 32] - s[:, 6]),
+                       ("  tile 4: dact2 (tile 5) -> LDS", s[:, 26] - s[:, 32]), ("  tile 4: X stage + refills", s[:, 27] - s[:, 26]),
+                       ("  tile 4: h1 recompute (tile 5)", s[:, 28] - s[:, 27]),
+                       ("  tile 4: (c) dW0 + db0 (tile 3)", s[:, 33] - s[:, 28]), ("  tile 4: barrier", s[:, 7] - s[:, 33])]
             for nm, v in sub:
                 print(f"  {nm:28s} median {np.median(v):9.0f}  max {v.max():9.0f} cycles")
         if k == 1 and bwd4 and producer is False and (s[:, 29] > 0).all():  # mlp_bwd4 consumer phases
