@@ -38,43 +38,14 @@ import torch
 
 from ..data.table import Table
 from ..ops import _native, rng
-from ..ops.gemm import EPI_BIAS_RELU, EPI_F32_SLAB, EPI_RELU_GRAD, gemm_bf16, tile_counts
-from .base import ClassificationModel, ClassifierParams, Estimator, dp_allreduce, dp_context, dp_owner, dp_rows, \
-    features_tensor, labels_tensor, new_uid, num_label_classes, resolve_device
-
-HEAD_PAD = 32  # classes padded to 32 rows (two 16-wide MFMA column tiles)
+from ..ops.gemm import EPI_BIAS_RELU, gemm_bf16
+from .base import ClassificationModel, ClassifierParams, Estimator, dp_context, dp_rows, features_tensor, \
+    labels_tensor, new_uid, num_label_classes, resolve_device
+from .mlp_paths import HEAD_PAD, FragCopies, FusedFwdPath, GemmPath, SmallPath, StepPath, n_splits_for
 
 
 def _pad(x: int, m: int) -> int:
     return (x + m - 1) // m * m
-
-
-def n_splits_for(batch: int) -> int:
-    """Batch slices of the split-K weight-gradient GEMMs (>= 1024-row slices, <= 64 slabs;
-    ``HAR_MLP_SPLITS`` overrides the slab cap for tuning)."""
-    cap = int(os.environ.get("HAR_MLP_SPLITS", "64"))
-    return max(1, min(cap, batch // max(1, 65536 // cap)))
-
-
-# Tile choices measured on MI355X with tools/gemm_bench.py (profiles/gemm_tile_sweep.md):
-# ids index ops.gemm.TILES = (BM, BN, BK).
-def fwd_tile(M: int, N: int, K: int) -> int:
-    if K <= 64:
-        return 12             # 64x128, BK 64
-    return 6 if N >= 256 else 12  # 128x256 reads each activation row once
-
-
-def dgrad_tile(M: int, N: int, K: int) -> int:
-    return 18 if N >= 256 else 12    # 128x128 / 8 waves (24.0 us vs 24.8 for 128x256 at B = 65536)
-
-
-def wgrad_tile(M: int, N: int) -> int:
-    """Weight-gradient (split-K over the batch) tiles (profiles/gemm_tile_sweep_v2.md)."""
-    if M <= 32:
-        return 11 if N > 32 else 2   # 32x64, BK 128
-    if N <= 64:
-        return 20                    # 64x64, BK 128, 8 waves: 13.1 us vs 14.4 (4 waves)
-    return 18                        # 128x128, BK 64, 8 waves: 23.4 us vs 30.0 (4 waves)
 
 
 @dataclass
@@ -196,312 +167,117 @@ class MLPEngine:
         self.G = self.Gfull[:n]
         self.m = torch.zeros_like(self.P)
         self.v = torch.zeros_like(self.P)
-        if self.sharded:
-            self.rank = _pg_rank(process_group)
-            self.lo = self.rank * self.chunk
-            self.n_own = max(0, min(n, self.lo + self.chunk) - self.lo)
-            self.Gsh = torch.zeros(self.chunk, dtype=torch.float32, device=dev)
+        self.rank = _pg_rank(process_group) if self.sharded else 0
+        self.lo = self.rank * self.chunk
+        self.n_own = max(0, min(n, self.lo + self.chunk) - self.lo)
+        self.Gsh = torch.zeros(self.chunk, dtype=torch.float32, device=dev) if self.sharded else None
         self.step_count = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.t_step = 0  # (the torch path's step counter)
         self.native = self.device.type == "cuda"
+        # native state (None on the torch path): the step paths this engine has (mlp_paths.py; None: its
+        # conditions do not hold), ``paths`` in the order they are asked, ``last``: the one that ran last
+        self.Pb = self.acts = self.dbuf = self.dims = self.slabs = self.last = None
+        # deterministic split-K: every weight-grad GEMM splits the batch into the same
+        # <= n_splits slices and writes plain partial tiles into slab z of a
+        # [n_splits, total] workspace laid out like the flat parameter buffer.
+        self.n_splits = n_splits_for(self.B)
+        # one-kernel forward + head + dWout (mlp_fused.hip) for the 2-hidden-layer shapes it covers
+        fused_ok = (self.native and len(L.hidden) == 2 and L.hidden[0] == L.hidden[1]
+                    and L.hidden[0] in (128, 256) and L.in_pad in (32, 64) and L.num_classes <= 16
+                    and os.environ.get("HAR_MLP_FUSED", "1") != "0")
+        # the three-kernel step (mlp_step.hip) for H = 256 and batches % 64 (HAR_MLP_STEP=0 keeps the fused
+        # forward + split-K GEMM backward, the reference path of the tests); small batches on one GPU
+        step_ok = fused_ok and L.hidden[0] == 256 and os.environ.get("HAR_MLP_STEP", "1") != "0"
+        small_ok = fused_ok and not self.dp and os.environ.get("HAR_MLP_SMALL", "1") != "0"
         if self.native:
+            mod = _native.kernels()
             self.Pb = self.P.to(torch.bfloat16)
-            dims = [L.in_pad] + L.hidden
+            self.dims = [L.in_pad] + L.hidden
             self.acts = [None] + [torch.empty(self.B, h, dtype=torch.bfloat16, device=dev) for h in L.hidden]
             hmax = max(L.hidden) if L.hidden else HEAD_PAD
             self.dbuf = [torch.empty(self.B * hmax, dtype=torch.bfloat16, device=dev) for _ in range(2)]
-            self.dlogits = torch.zeros(self.B, HEAD_PAD, dtype=torch.bfloat16, device=dev)
-            nblk = _native.kernels().head_fused_blocks(self.B)
-            self.block_loss = torch.zeros(nblk, dtype=torch.float32, device=dev)
-            self.block_correct = torch.zeros(nblk, dtype=torch.int32, device=dev)
-            self.dims = dims
-            # deterministic split-K: every weight-grad GEMM splits the batch into the same
-            # <= n_splits slices and writes plain partial tiles into slab z of a
-            # [n_splits, total] workspace laid out like the flat parameter buffer.
-            self.n_splits = n_splits_for(self.B)
-            # the step backward (mlp_step.hip) writes one partial per row slice into the same slabs
-            n_slab = max(self.n_splits, _native.kernels().mlp_step_slices(self.B))
+            # (the step backward writes one partial per row slice, the small step one per tile, into them)
+            n_slab = max(self.n_splits, mod.mlp_step_slices(self.B),
+                         mod.mlp_small_step_max_batch() // 32 if small_ok else 0)
             self.slabs = torch.zeros(n_slab, L.total, dtype=torch.float32, device=dev)
-            # one-kernel forward + head + dWout (mlp_fused.hip) for the 2-hidden-layer shapes it covers
-            self.fused_ok = (len(L.hidden) == 2 and L.hidden[0] == L.hidden[1] and L.hidden[0] in (128, 256)
-                             and L.in_pad in (32, 64) and L.num_classes <= 16
-                             and os.environ.get("HAR_MLP_FUSED", "1") != "0")
-            if self.fused_ok:
-                nwg = _native.kernels().mlp_fwd_head_grid(self.B)
-                H = L.hidden[-1]  # per workgroup: dWout rows 0..15 [16][H], dbout [16] (+ an unused db1 slot)
-                self.fslab = torch.zeros(nwg, 16 * H + 16 + H, dtype=torch.float32, device=dev)
-                self.fblock_loss = torch.zeros(nwg, dtype=torch.float32, device=dev)
-                self.fblock_correct = torch.zeros(nwg, dtype=torch.int32, device=dev)
-            self.last_fused = False
-            # the three-kernel step (mlp_step.hip: forward -> dz + relu' mask, backward rebuilding dact2
-            # and h1 on chip, then grad_reduce_adam) for H = 256 and batches % 64; HAR_MLP_STEP=0 keeps
-            # the fused forward + split-K GEMM backward (the reference path of the tests)
-            self.step_ok = (self.fused_ok and L.hidden[0] == 256
-                            and os.environ.get("HAR_MLP_STEP", "1") != "0")
-            if self.step_ok:
-                mod = _native.kernels()
-                nwg = mod.mlp_step_grid(self.B)
-                self.sslab = torch.zeros(nwg, mod.mlp_step_fwd_slab_width(256), dtype=torch.float32, device=dev)
-                self.sblock_loss = torch.zeros(nwg, dtype=torch.float32, device=dev)
-                self.sblock_correct = torch.zeros(nwg, dtype=torch.int32, device=dev)
-                # the layer-2 gradient dact2 the forward writes for the backward (bf16 [B][256], the
-                # backward's LDS tile order: 16-byte chunks of rows with bit 2 set swapped in pairs)
-                self.dact2 = torch.zeros(self.B * L.hidden[-1], dtype=torch.bfloat16, device=dev)
-                # MFMA-fragment-ordered bf16 copies of W0 / W1 (W0 | W1 | W1^T; mlp.hip frag_pos): the step
-                # kernels load their weight operands from here, one 1 KB-contiguous load per fragment;
-                # every Adam update of the step refreshes them together with Pb
-                H = L.hidden[0]
-                self.Pf = torch.zeros(H * L.in_pad + 2 * H * H, dtype=torch.bfloat16, device=dev)
-                self._pack_frag()
-            # small batches (B <= 512, B % 32 == 0, one GPU): the whole forward + backward of each 32-row
-            # tile in one workgroup (mlp_small.hip) + the reduction / Adam kernel — two launches per step
-            self.small_ok = (self.fused_ok and L.hidden[0] in (128, 256) and not self.dp
-                             and os.environ.get("HAR_MLP_SMALL", "1") != "0")
-            self.small_max = _native.kernels().mlp_small_step_max_batch() if self.small_ok else 0
-            if self.small_ok:
-                H = L.hidden[0]
-                if not getattr(self, "step_ok", False):  # (the step path allocated them already)
-                    self.Pf = torch.zeros(H * L.in_pad + 2 * H * H, dtype=torch.bfloat16, device=dev)
-                self.small_loss = torch.zeros(self.small_max // 32, dtype=torch.float32, device=dev)
-                self.small_correct = torch.zeros(self.small_max // 32, dtype=torch.int32, device=dev)
-                if self.slabs.shape[0] < self.small_max // 32:
-                    self.slabs = torch.zeros(self.small_max // 32, L.total, dtype=torch.float32, device=dev)
-                self._pack_frag()
-            # the W1^T fragment copy equals the current W1 (only the small path's Adam keeps it so; the
-            # step path's forward writes it from the pre-update W1, the other paths leave it)
-            self._pf_fresh = True
-            self.last_bwd = False
-            self.last_path = None
-            # optional: the two backward branches after the fused forward — dW1 (split-K over the
-            # batch) and dgrad -> dW0 — are independent, so HAR_MLP_STREAMS=1 runs dW1 on a second
-            # HIP stream (fork/join with events; graph-capturable).  Measured on MI355X at batch
-            # 65536: 0.147 vs 0.141 ms/step — both branches already fill every CU — so it is off.
-            self.side = torch.cuda.Stream(dev) if os.environ.get("HAR_MLP_STREAMS", "0") == "1" else None
-            self.ev_fork = torch.cuda.Event() if self.side is not None else None
-            self.ev_join = torch.cuda.Event() if self.side is not None else None
-        else:
-            self.t_step = 0
+        self.frag = FragCopies(self, on=step_ok or small_ok, in_adam=step_ok)
+        self.gemm = GemmPath(self) if self.native else None
+        self.fused = FusedFwdPath(self) if fused_ok else None
+        self.step = StepPath(self) if step_ok else None
+        self.small = SmallPath(self) if small_ok else None
+        self.paths = [p for p in (self.small, self.step, self.fused, self.gemm) if p is not None]
+
+    # What the tests, the tools and the drivers read: derived from the paths, which own the state.
+    step_ok = property(lambda self: self.step is not None)
+    small_ok = property(lambda self: self.small is not None)
+    last_path = property(lambda self: self.last.name if self.last else None)
+    last_fused = property(lambda self: bool(self.last and self.last.fused))
+    last_bwd = property(lambda self: bool(self.last and self.last.ticks))
+    Pf = property(lambda self: self.frag.Pf)
+    _pf_fresh = property(lambda self: self.frag.fresh)
+    step_S = property(lambda self: self.step.S if self.step else 0)
+    dact2 = property(lambda self: self.step.dact2 if self.step else None)
+    fslab = property(lambda self: self.fused.slab if self.fused else None)
+    fblock_loss = property(lambda self: self.fused.loss if self.fused else None)
+    fblock_correct = property(lambda self: self.fused.correct if self.fused else None)
+
+    fused_ok = property(lambda self: self.fused is not None)
+
+    @fused_ok.setter
+    def fused_ok(self, on: bool):  # off, on a live engine (the tests' unfused reference): gemm alone is left
+        assert not on, "the fused kernels are chosen at construction (HAR_MLP_FUSED)"
+        self.fused = self.step = self.small = None
+        self.paths = self.paths[-1:]
 
     # ---------------------------------------------------------------- native
     def _w(self, flat, name):
         return self.layout.view(flat, name)
 
-    def _frag_args(self):
-        """(dst, W0 offset, W1 offset, K0, H) of the fragment copies, or zeros when the step is off."""
-        if not getattr(self, "step_ok", False):
-            return 0, 0, 0, 0, 0
-        L = self.layout
-        return (self.Pf.data_ptr(), L.by_name["W0"].offset, L.by_name["W1"].offset, L.in_pad, L.hidden[0])
-
-    def _pack_frag(self):
-        """Rebuild the fragment copies (W0 | W1 | W1^T) from Pb (after anything but the step's Adam wrote Pb)."""
-        if getattr(self, "Pf", None) is not None:
-            L = self.layout
-            _native.kernels().mlp_pack_frag(self.Pb.data_ptr(), self.Pf.data_ptr(), L.by_name["W0"].offset,
-                                            L.by_name["W1"].offset, L.in_pad, L.hidden[0], _native.stream_ptr())
-            self._pf_fresh = True
-
-    def _small_ok(self, Xb, yb) -> bool:
-        B = Xb.shape[0]
-        return (getattr(self, "small_ok", False) and 0 < B <= self.small_max and B % 32 == 0
-                and Xb.shape[1] == self.layout.in_pad and Xb.dtype == torch.bfloat16 and Xb.is_contiguous()
-                and yb.dtype == torch.int32)
-
-    def _small_step(self, Xb, yb, global_batch: int):
-        """mlp_small.hip: the fused tile kernel + the reduction / Adam of its B / 32 slabs (one host call)."""
-        L, B = self.layout, Xb.shape[0]
-        if not self._pf_fresh:  # a step of another path ran since: W1^T (and for H = 128 W0 / W1) re-packed
-            self._pack_frag()
-        b1, b2 = self.betas
-        o = {n: L.by_name[n].offset for n in ("W0", "b0", "W1", "b1", "Wout", "bout")}
-        _native.kernels().mlp_small_step(
-            Xb.data_ptr(), L.in_pad, self.Pf.data_ptr(), self._w(self.P, "b0").data_ptr(),
-            self._w(self.P, "b1").data_ptr(), L.hidden[0], self._w(self.Pb, "Wout").data_ptr(),
-            self._w(self.P, "bout").data_ptr(), yb.data_ptr(), B, L.num_classes, 1.0 / global_batch,
-            self.slabs.data_ptr(), L.total, o["W0"], o["b0"], o["W1"], o["b1"], o["Wout"], o["bout"],
-            self.small_loss.data_ptr(), self.small_correct.data_ptr(), self.step_count.data_ptr(), self.G.data_ptr(),
-            self.P.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.Pb.data_ptr(), float(self.lr), b1, b2,
-            float(self.eps), float(self.wd), self.step_count.data_ptr(), _native.stream_ptr())
-        self.last_path, self.last_fused, self.last_bwd, self.last_batch = "small", False, True, B
-        self._pf_fresh = True
-
     def refresh_bf16(self):
         """Pb (+ fragment copies) from the fp32 master P."""
         if self.native:
             self.Pb.copy_(self.P.to(torch.bfloat16))
-            self._pack_frag()
+            self.frag.pack()
 
     def _refresh_native(self):
         """Pb and every fragment copy (W0 | W1 | W1^T) rebuilt from P by ONE kernel (grad_reduce_adam,
         GR_REFRESH): the sharded DP step after its all-gather of P.  Bitwise the torch cast + pack
         it replaces (the same round-to-nearest-even conversion)."""
-        dst, w0, w1, k0, h = self._frag_args()
-        if not dst and getattr(self, "Pf", None) is not None:  # (small path only: Pf without the step)
-            L = self.layout
-            dst, w0, w1, k0, h = self.Pf.data_ptr(), L.by_name["W0"].offset, L.by_name["W1"].offset, L.in_pad, L.hidden[0]
-        b1, b2 = self.betas
-        _native.kernels().grad_reduce_adam(
-            [], [], [], [], [], self.layout.total, self.G.data_ptr(), self.P.data_ptr(), self.m.data_ptr(),
-            self.v.data_ptr(), self.Pb.data_ptr(), float(self.lr), b1, b2, float(self.eps), float(self.wd),
-            self.step_count.data_ptr(), 0, self.GR_REFRESH, _native.stream_ptr(), dst, w0, w1, k0, h, 1 if dst else 0)
-        if dst:
-            self._pf_fresh = True
+        self._grad_kernel(self.GR_REFRESH, frag=(*self.frag.args, int(self.Pf is not None)))
+        self.frag.fresh = True
 
     def _slab(self, name):
         s = self.layout.by_name[name]
         return self.slabs.view(-1)[s.offset:]
+
+    def select(self, Xb: torch.Tensor, yb: torch.Tensor, whole_step: bool = True):
+        """THE selector: the first of small, step, fused_fwd, gemm that takes the batch (Xb: [B, in_pad] bf16,
+        contiguous; yb: [B] int32).  ``whole_step=False``: not those that only run whole steps (small)."""
+        if (Xb.shape[1] == self.layout.in_pad and Xb.dtype == torch.bfloat16 and yb.dtype == torch.int32
+                and Xb.is_contiguous()):
+            for p in self.paths:
+                if (whole_step or not p.whole_step) and p.takes(Xb, yb):
+                    return p
+        raise ValueError("bad batch")
+
+    def _start(self, Xb, yb, whole_step: bool = True):
+        """``select`` for a batch that now runs: the path becomes ``last`` (and the rule of FragCopies)."""
+        path = self.last = self.select(Xb, yb, whole_step)
+        if not path.keeps_frag:
+            self.frag.mark_stale()
+        return path
+
+    def graph_ok(self, Xb, yb) -> bool:
+        """Steps on such batches may be captured into one HIP graph per epoch: the three-kernel step or the
+        fused forward + split-K backward takes them (or the small step in their place at a small batch)."""
+        return self.native and self.select(Xb, yb, whole_step=False).fused
 
     def forward_backward_native(self, Xb: torch.Tensor, y32: torch.Tensor, scale: float, on_grad=None,
                                 _record=None):
         """Xb: [B, in_pad] bf16 (contiguous slice), y32: [B] int32.  Leaves the gradient partials
         in the slabs (``_grad_regions``); ``on_grad(name)`` is called as soon as layer ``name``'s
         weight/bias gradient slabs are enqueued (a hook for tracing / tests)."""
-        L, mod, s = self.layout, _native.kernels(), _native.stream_ptr()
-        B = Xb.shape[0]
-        if Xb.shape[1] != L.in_pad or Xb.dtype != torch.bfloat16 or B > self.B or y32.dtype != torch.int32:
-            raise ValueError("bad batch")
-        ks = max(128, ((B + self.n_splits - 1) // self.n_splits + 127) // 128 * 128)  # multiple of every BK
-        self.active_splits = (B + ks - 1) // ks
-        total = L.total
-        nh = len(L.hidden)
-        acts = [Xb] + [a[:B] for a in self.acts[1:]]
-        if self.step_ok and B % 64 == 0:
-            return self._step(Xb, y32, scale, on_grad, _record)
-        if self.fused_ok and B % 16 == 0:
-            return self._forward_backward_fused(Xb, y32, scale, on_grad, ks, acts, _record)
-        self.last_fused = False
-        self.last_bwd = False
-        self.last_path = "gemm"
-        for i in range(nh):
-            gemm_bf16(acts[i], self._w(self.Pb, f"W{i}"), acts[i + 1], M=B, N=self.dims[i + 1], K=self.dims[i],
-                      layout=0, epi=EPI_BIAS_RELU, bias=self._w(self.P, f"b{i}"),
-                      tile=fwd_tile(B, self.dims[i + 1], self.dims[i]))
-        last = acts[nh]
-        if nh == 0:
-            raise ValueError("the native MLP step needs at least one hidden layer")
-        # fused head: CE loss, dlogits, and dact of the last hidden layer = (dlogits . Wout) * relu'
-        dact = self.dbuf[(nh - 1) % 2][: B * self.dims[-1]].view(B, self.dims[-1])
-        mod.head_fused(last.data_ptr(), self._w(self.Pb, "Wout").data_ptr(), self._w(self.P, "bout").data_ptr(),
-                       y32.data_ptr(), B, self.dims[-1], L.num_classes, float(scale), self.dlogits.data_ptr(),
-                       dact.data_ptr(), self.block_loss.data_ptr(), self.block_correct.data_ptr(), s)
-        self.last_batch = B
-        dl = self.dlogits[:B]
-        # dWout = dlogits^T . last  (+ dbout = row sums of dlogits^T)
-        gemm_bf16(dl, last, self._slab("Wout"), M=HEAD_PAD, N=self.dims[-1], K=B, layout=3, epi=EPI_F32_SLAB,
-                  k_split=ks, ldc=self.dims[-1], slab_stride=total, rowsum=self._slab("bout"),
-                  slab_stride_rowsum=total, tile=wgrad_tile(HEAD_PAD, self.dims[-1]))
-        if on_grad is not None:
-            on_grad("Wout")
-        for i in reversed(range(nh)):
-            h = self.dims[i + 1]
-            # dW_i = dact^T . acts[i]   (+ db_i = row sums of dact^T)
-            gemm_bf16(dact, acts[i], self._slab(f"W{i}"), M=h, N=self.dims[i], K=B, layout=3, epi=EPI_F32_SLAB,
-                      k_split=ks, ldc=self.dims[i], slab_stride=total, rowsum=self._slab(f"b{i}"),
-                      slab_stride_rowsum=total, tile=wgrad_tile(h, self.dims[i]))
-            if on_grad is not None:
-                on_grad(f"W{i}")
-            if i > 0:
-                # dact_{i-1} = (dact . W_i) * relu'(acts[i])
-                hp = self.dims[i]
-                prev = self.dbuf[(i - 1) % 2][: B * hp].view(B, hp)
-                gemm_bf16(dact, self._w(self.Pb, f"W{i}"), prev, M=B, N=hp, K=h, layout=2, epi=EPI_RELU_GRAD,
-                          mask=acts[i], tile=dgrad_tile(B, hp, h))
-                dact = prev
-
-    def _step(self, Xb, y32, scale, on_grad, record=None):
-        """The three-kernel step of the H = 256 network (mlp_step.hip): mlp_step_fwd (layer 1, layer 2,
-        softmax-CE head, dWout / dbout, and dact2 = (dz . Wout) * relu'(h2) in bf16), mlp_step_bwd (h1
-        recomputed, dW1 + dgrad + relu' + dW0 / db0 / db1 in one pass).  The
-        gradient reduction + Adam follow in ``train_step``.  ``record`` (a list) receives one
-        re-launchable closure per kernel (tools/mlp_phase_probe.py)."""
-        L, mod = self.layout, _native.kernels()
-        B, H, K0 = Xb.shape[0], self.dims[-1], L.in_pad
-        total = L.total
-        self.step_nwg = mod.mlp_step_grid(B)
-        self.step_S = mod.mlp_step_slices(B)
-        P, Pb, sb = self.P, self.Pb, self.slabs.data_ptr()
-        w = lambda t, n: self._w(t, n).data_ptr()  # noqa: E731
-
-        def fwd():
-            mod.mlp_step_fwd(Xb.data_ptr(), K0, self.Pf.data_ptr(), w(P, "b0"), w(P, "b1"), H, w(Pb, "Wout"),
-                             w(P, "bout"), y32.data_ptr(), B, L.num_classes, float(scale), self.dact2.data_ptr(),
-                             self.sslab.data_ptr(), self.sblock_loss.data_ptr(),
-                             self.sblock_correct.data_ptr(), _native.stream_ptr())
-
-        def bwd():  # also sums the forward's dWout / dbout slabs into G
-            off = lambda n: sb + 4 * L.by_name[n].offset  # noqa: E731
-            mod.mlp_step_bwd(self.dact2.data_ptr(), Xb.data_ptr(), K0, self.Pf.data_ptr(), H,
-                             w(P, "b0"), B, off("W1"), off("W0"), off("b0"), off("b1"),
-                             total, self.step_count.data_ptr(), self.sslab.data_ptr(), self.sslab.shape[1],
-                             w(self.G, "Wout"), w(self.G, "bout"), _native.stream_ptr())
-
-        fwd()
-        if on_grad is not None:
-            on_grad("Wout")
-        bwd()
-        if on_grad is not None:
-            on_grad("W1")
-            on_grad("W0")
-        if record is not None:
-            record += [fwd, bwd]
-        self.last_fused = self.last_bwd = True
-        self.last_path = "step"
-        self.last_batch = B
-
-    def _forward_backward_fused(self, Xb, y32, scale, on_grad, ks, acts, record=None):
-        """2-hidden-layer step of the shapes the three-kernel step does not take (H = 128, or a batch
-        that is not a multiple of 64): ONE kernel for fwd L1 + fwd L2 + head + dWout/dbout (h2 and
-        the logit gradients stay on chip; h1 and dact2 are written), then dW1, dgrad and dW0 as
-        split-K MFMA GEMMs."""
-        L, mod, s = self.layout, _native.kernels(), _native.stream_ptr()
-        B, H, K0 = Xb.shape[0], self.dims[-1], L.in_pad
-        total = L.total
-        h1 = acts[1]
-        dact = self.dbuf[1][: B * H].view(B, H)
-        self.fused_nwg = mod.mlp_fwd_head_grid(B)
-
-        def fwd():
-            mod.mlp_fwd_head(Xb.data_ptr(), K0, self._w(self.Pb, "W0").data_ptr(), self._w(self.P, "b0").data_ptr(),
-                             self._w(self.Pb, "W1").data_ptr(), self._w(self.P, "b1").data_ptr(), H,
-                             self._w(self.Pb, "Wout").data_ptr(), self._w(self.P, "bout").data_ptr(),
-                             y32.data_ptr(), B, L.num_classes, float(scale), h1.data_ptr(), dact.data_ptr(),
-                             self.fslab.data_ptr(), self.fblock_loss.data_ptr(), self.fblock_correct.data_ptr(), s)
-
-        fwd()
-        if record is not None:
-            record.append(fwd)
-        self.last_fused = True
-        self.last_bwd = False
-        self.last_path = "fused_fwd"
-        self.last_batch = B
-        if on_grad is not None:
-            on_grad("Wout")
-
-        def dw1():
-            gemm_bf16(dact, h1, self._slab("W1"), M=H, N=H, K=B, layout=3, epi=EPI_F32_SLAB, k_split=ks, ldc=H,
-                      slab_stride=total, rowsum=self._slab("b1"), slab_stride_rowsum=total, tile=wgrad_tile(H, H))
-
-        prev = self.dbuf[0][: B * H].view(B, H)
-        main = torch.cuda.current_stream(self.device)
-        if self.side is not None:  # fork: dW1 on the side stream, dgrad -> dW0 here
-            self.ev_fork.record(main)
-            self.side.wait_event(self.ev_fork)
-            with torch.cuda.stream(self.side):
-                dw1()
-                if on_grad is not None:
-                    on_grad("W1")
-                self.ev_join.record(self.side)
-        else:
-            dw1()
-            if on_grad is not None:
-                on_grad("W1")
-        gemm_bf16(dact, self._w(self.Pb, "W1"), prev, M=B, N=H, K=H, layout=2, epi=EPI_RELU_GRAD, mask=h1,
-                  tile=dgrad_tile(B, H, H))
-        gemm_bf16(prev, Xb, self._slab("W0"), M=H, N=K0, K=B, layout=3, epi=EPI_F32_SLAB, k_split=ks, ldc=K0,
-                  slab_stride=total, rowsum=self._slab("b0"), slab_stride_rowsum=total, tile=wgrad_tile(H, K0))
-        if on_grad is not None:
-            on_grad("W0")
-        if self.side is not None:  # join: the W1 slabs (and the next step's h1 / dact2 reuse) are ordered
-            main.wait_event(self.ev_join)
+        self._start(Xb, y32, whole_step=False).forward_backward(Xb, y32, scale, on_grad, _record)
 
     def phase_fns(self, Xb: torch.Tensor, y32: torch.Tensor, global_batch: int):
         """One callable per kernel of the fused step (forward, backward, reduction + Adam), for
@@ -509,50 +285,23 @@ class MLPEngine:
         step left behind."""
         self.forward_backward_native(Xb, y32, 1.0 / global_batch)
         calls = []
-
-        def fb():
-            self.forward_backward_native(Xb, y32, 1.0 / global_batch, _record=calls)
-
-        fb()
-        out = {}
-        if calls:
-            out["fwd"] = calls[0]
-            if len(calls) > 1:
-                out["bwd"] = calls[1]
-        out["reduce"] = lambda: self._grad_kernel(self.GR_REDUCE | self.GR_ADAM, tick=not self.last_bwd)
+        self.forward_backward_native(Xb, y32, 1.0 / global_batch, _record=calls)
+        out = dict(zip(("fwd", "bwd"), calls))
+        out["reduce"] = lambda: self._grad_kernel(self.GR_REDUCE | self.GR_ADAM, tick=not self.last.ticks)
         return out
 
     def _grad_regions(self):
         """Sources of the flat gradient after the last native batch, in flat order: (start, end,
-        pointer of slab 0 at start, #slabs, slab stride) — the step backward's per-slice partials
-        (W0, b0, W1, b1) and the step forward's per-workgroup dWout / dbout slabs, or the split-K
-        GEMM slabs (+ the fused forward's dWout / dbout slabs)."""
-        L, total = self.layout, self.layout.total
-        regions = []
-        wo, bo = L.by_name["Wout"].offset, L.by_name["bout"].offset
-        if self.last_path == "step":
-            H = self.dims[-1]
-            w0, b1 = L.by_name["W0"].offset, L.by_name["b1"].offset
-            regions.append((w0, b1 + H, self.slabs.data_ptr() + 4 * w0, self.step_S, total))  # W0, b0, W1, b1
-            g = self.G.data_ptr()  # dWout / dbout: summed into G by the step backward
-            regions.append((wo, wo + 16 * H, g + 4 * wo, 1, 4))
-            regions.append((bo, bo + 16, g + 4 * bo, 1, 4))
-            return regions
-        end = wo if self.last_fused else total
-        regions.append((0, end, self.slabs.data_ptr(), self.active_splits, total))
-        if self.last_fused:
-            H, w = self.dims[-1], self.fslab.shape[1]
-            fs = self.fslab.data_ptr()
-            regions.append((wo, wo + 16 * H, fs, self.fused_nwg, w))
-            regions.append((bo, bo + 16, fs + 4 * 16 * H, self.fused_nwg, w))
-        return regions
+        pointer of slab 0 at start, #slabs, slab stride)."""
+        return self.last.regions()
 
     GR_REDUCE, GR_STORE, GR_ADAM, GR_REFRESH = 1, 2, 4, 8
 
-    def _grad_kernel(self, mode: int, tick: bool = False):
+    def _grad_kernel(self, mode: int, tick: bool = False, frag=None):
         """mlp.hip grad_reduce_adam: one deterministic single-level reduction of every gradient
         slab (fixed order) and/or the Adam update; the same kernel for every world size.  The
-        step counter ticks once per step: in the fused backward kernel, else here (``tick``)."""
+        step counter ticks once per step: in the fused backward kernel, else here (``tick``).
+        ``frag``: the fragment copies it rewrites (default: those Adam keeps current)."""
         b1, b2 = self.betas
         regs = self._grad_regions() if mode & self.GR_REDUCE else []
         cols = list(zip(*regs)) if regs else [[]] * 5
@@ -560,11 +309,11 @@ class MLPEngine:
             list(cols[2]), list(cols[0]), [e - a for a, e in zip(cols[0], cols[1])], list(cols[4]), list(cols[3]),
             self.layout.total, self.G.data_ptr(), self.P.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
             self.Pb.data_ptr(), float(self.lr), b1, b2, float(self.eps), float(self.wd), self.step_count.data_ptr(),
-            int(tick), mode, _native.stream_ptr(), *self._frag_args())
+            int(tick), mode, _native.stream_ptr(), *(frag or self.frag.adam_args))
 
     def reduce_grads_native(self):
         """G = the sum of the last batch's gradient slabs (needed before a collective)."""
-        self._grad_kernel(self.GR_REDUCE | self.GR_STORE, tick=not self.last_bwd)
+        self._grad_kernel(self.GR_REDUCE | self.GR_STORE, tick=not self.last.ticks)
 
     def optimizer_step_native(self):
         """Adam from G (after the all-reduce; the step counter ticked with the gradient)."""
@@ -577,7 +326,7 @@ class MLPEngine:
         all-reduce step (smaller models, e.g. 43-256-256-6's ~0.34 MB: latency-bound on xGMI, so one
         flat message, no bucketing) is ONE all-reduce of G."""
         if not self.dp:
-            return {"all_reduce": 0, "bytes": 0, "kernels": 3 if getattr(self, "step_ok", False) else None}
+            return {"all_reduce": 0, "bytes": 0, "kernels": 3 if self.step_ok else None}
         if self.sharded:
             nb = int(self.Gfull.numel() * 4)
             # kernels: forward, backward, reduction -> G | Adam on the owned slice | Pb + fragment refresh
@@ -657,14 +406,7 @@ class MLPEngine:
         """DP step, part 1 (graph-capturable): fwd + bwd + deterministic slab reduction into G."""
         if not self.native:
             return self._grad_torch(Xb, yb, global_batch)
-        if self._plan_ok(Xb, yb):
-            B = Xb.shape[0]
-            plan, self.step_nwg, self.step_S = self._plan(B)
-            self.last_path, self.last_fused, self.last_bwd, self.last_batch = "step", True, True, B
-            plan.run(Xb.data_ptr(), yb.data_ptr(), B, 1.0 / global_batch, 2, _native.stream_ptr())
-            return
-        self.forward_backward_native(Xb, yb, 1.0 / global_batch)
-        self.reduce_grads_native()
+        self._start(Xb, yb, whole_step=False).run(Xb, yb, global_batch, adam=False)
 
     def apply_phase(self):
         """DP step, part 3 (graph-capturable): Adam from the all-reduced G (part 2 is the RCCL
@@ -676,87 +418,24 @@ class MLPEngine:
             return self._adam_torch()
         self.optimizer_step_native()
 
-    def _plan(self, B: int):
-        """The native step plan (bind.cpp MlpStepPlan) of the three-kernel step at batch B: every
-        pointer, gradient region and hyper-parameter fixed once, so a step is ONE host call."""
-        plans = self.__dict__.setdefault("_plans", {})
-        if B not in plans:
-            L, mod = self.layout, _native.kernels()
-            self.step_nwg, self.step_S = mod.mlp_step_grid(B), mod.mlp_step_slices(B)
-            self.last_path, self.last_fused, self.last_bwd = "step", True, True
-            sb = self.slabs.data_ptr()
-            off = lambda n: sb + 4 * L.by_name[n].offset  # noqa: E731
-            w = lambda t, n: self._w(t, n).data_ptr()  # noqa: E731
-            P, Pb = self.P, self.Pb
-            d = dict(Wf=self.Pf.data_ptr(), w0_off=L.by_name["W0"].offset, w1_off=L.by_name["W1"].offset,
-                     b0=w(P, "b0"), b1=w(P, "b1"), Wo=w(Pb, "Wout"), bo=w(P, "bout"),
-                     dact2=self.dact2.data_ptr(), fslab=self.sslab.data_ptr(),
-                     bloss=self.sblock_loss.data_ptr(), bcorr=self.sblock_correct.data_ptr(), gw1=off("W1"),
-                     gw0=off("W0"), gb0=off("b0"), gb1=off("b1"), step=self.step_count.data_ptr(),
-                     fslab_w=self.sslab.shape[1], gwo=w(self.G, "Wout"), gbo=w(self.G, "bout"),
-                     G=self.G.data_ptr(), P=P.data_ptr(), m=self.m.data_ptr(), v=self.v.data_ptr(), Pb=Pb.data_ptr(),
-                     K0=L.in_pad, H=self.dims[-1], C=L.num_classes, stride=L.total, n=L.total, lr=float(self.lr),
-                     beta1=float(self.betas[0]), beta2=float(self.betas[1]), eps=float(self.eps), wd=float(self.wd),
-                     regions=[(a, e, p, ns, ld) for a, e, p, ns, ld in self._grad_regions()])
-            plan = mod.MlpStepPlan(d)
-            if getattr(self, "pf_sink", None) is None:  # scratch word of the reduction's prefetch workgroups
-                self.pf_sink = torch.zeros(4, dtype=torch.int32, device=self.device)
-            if hasattr(plan, "pf_sink"):  # (absent from a library built before the prefetch: A/B runs)
-                plan.pf_sink = self.pf_sink.data_ptr()
-            plans[B] = (plan, self.step_nwg, self.step_S)
-        return plans[B]
-
-    def _plan_ok(self, Xb, yb):
-        return (self.step_ok and Xb.shape[0] % 64 == 0 and Xb.shape[0] <= self.B and Xb.shape[1] == self.layout.in_pad
-                and Xb.dtype == torch.bfloat16 and yb.dtype == torch.int32 and Xb.is_contiguous()
-                and os.environ.get("HAR_MLP_PLAN", "1") != "0")
-
     def train_step(self, Xb: torch.Tensor, yb: torch.Tensor, global_batch: int, prefetch=None):
         """One step.  Native: fwd kernel + bwd kernel + ONE reduction kernel; at N = 1 the Adam
         update is fused into that kernel, at N > 1 it stores G, one RCCL all-reduce of G follows and
         Adam runs from G — the same kernels and the same summation order at every N.  The
-        three-kernel step goes through the native plan (one host call per phase).  ``prefetch``: the
-        next step's input rows (a device tensor, or a (rows, labels) pair), read once per cache line by extra workgroups of this
+        three-kernel step goes through the native plan (one host call per phase).  ``prefetch``: the next
+        step's input rows (a device tensor, or a (rows, labels) pair), read by extra workgroups of this
         step's reduction launch, so the next forward finds them in the memory-side cache — for epochs
         over more rows than it holds (reads only: the step's results do not depend on it; the other
         step paths ignore it)."""
-        if self.native and not self.dp and self._small_ok(Xb, yb):
-            return self._small_step(Xb, yb, global_batch)
-        if self.native:
-            self._pf_fresh = False  # (every other native path leaves the W1^T copy behind W1)
-        if self.native and self._plan_ok(Xb, yb):
-            B = Xb.shape[0]
-            plan, self.step_nwg, self.step_S = self._plan(B)
-            self.last_path, self.last_fused, self.last_bwd, self.last_batch = "step", True, True, B
-            s = _native.stream_ptr()
-            pf = []  # (pointer, bytes) of up to two regions; none: the plain launch
-            regions = prefetch if isinstance(prefetch, (tuple, list)) else (prefetch,)
-            for t in regions:
-                if t is not None and t.is_cuda and t.numel():
-                    pf += [t.data_ptr(), t.numel() * t.element_size()]
-            if self.dp:
-                plan.run(Xb.data_ptr(), yb.data_ptr(), B, 1.0 / global_batch, 2, s, *pf)
-                if self.sharded:
-                    self.sharded_update()
-                else:
-                    self.allreduce_grads()
-                    plan.run(0, 0, B, 0.0, 4, s)
-            else:
-                plan.run(Xb.data_ptr(), yb.data_ptr(), B, 1.0 / global_batch, 1, s, *pf)
-            return
-        if self.native:
-            self.forward_backward_native(Xb, yb, 1.0 / global_batch)
-            if self.dp:
-                self.reduce_grads_native()
-                if self.sharded:
-                    self.sharded_update()
-                else:
-                    self.allreduce_grads()
-                    self.optimizer_step_native()
-            else:
-                self._grad_kernel(self.GR_REDUCE | self.GR_ADAM, tick=not self.last_bwd)
-        else:
-            self.train_step_torch(Xb, yb, global_batch)
+        if not self.native:
+            return self.train_step_torch(Xb, yb, global_batch)
+        path = self._start(Xb, yb)
+        path.run(Xb, yb, global_batch, not self.dp, prefetch)
+        if self.sharded:
+            self.sharded_update()
+        elif self.dp:
+            self.allreduce_grads()
+            path.adam()
 
     def state_tensors(self):
         """Everything needed to resume training bit-for-bit (sharded optimizer: the moments are
@@ -777,16 +456,7 @@ class MLPEngine:
 
     def last_loss_and_correct(self):
         """(sum of CE, #correct) of the last native batch — one host sync."""
-        if self.last_path == "step":
-            n = self.step_nwg
-            return float(self.sblock_loss[:n].sum().item()), int(self.sblock_correct[:n].sum().item())
-        if self.last_path == "small":
-            n = self.last_batch // 32
-            return float(self.small_loss[:n].sum().item()), int(self.small_correct[:n].sum().item())
-        if self.last_fused:
-            n = self.fused_nwg
-            return float(self.fblock_loss[:n].sum().item()), int(self.fblock_correct[:n].sum().item())
-        return float(self.block_loss.sum().item()), int(self.block_correct.sum().item())
+        return self.last.loss_and_correct()
 
     # ---------------------------------------------------------------- torch
     def torch_forward(self, P: torch.Tensor, X: torch.Tensor):
@@ -837,11 +507,8 @@ class MLPEngine:
             raise ValueError("infer_fused: unsupported shape")
         out = torch.empty(B, L.num_classes, dtype=torch.float32, device=Xb.device)
         pred = torch.empty(B, dtype=torch.int32, device=Xb.device)
-        _native.kernels().mlp_fwd_infer(Xb.data_ptr(), L.in_pad, self._w(self.Pb, "W0").data_ptr(),
-                                        self._w(self.P, "b0").data_ptr(), self._w(self.Pb, "W1").data_ptr(),
-                                        self._w(self.P, "b1").data_ptr(), self.dims[-1],
-                                        self._w(self.Pb, "Wout").data_ptr(), self._w(self.P, "bout").data_ptr(), B,
-                                        L.num_classes, out.data_ptr(), pred.data_ptr(), _native.stream_ptr())
+        _native.kernels().mlp_fwd_infer(Xb.data_ptr(), *self.fused.net, B, L.num_classes, out.data_ptr(),
+                                        pred.data_ptr(), _native.stream_ptr())
         return out, pred
 
     def infer_fused_f32(self, X: torch.Tensor):
@@ -853,14 +520,13 @@ class MLPEngine:
             raise ValueError("infer_fused_f32: unsupported shape")
         out = torch.empty(B, L.num_classes, dtype=torch.float32, device=X.device)
         pred = torch.empty(B, dtype=torch.int32, device=X.device)
-        if (getattr(self, "Pf", None) is not None and L.hidden[0] == 256 and B % 64 == 0
+        if (self.Pf is not None and L.hidden[0] == 256 and B % 64 == 0
                 and os.environ.get("HAR_MLP_STEP_INFER", "1") != "0"):
             # the training step's forward pipeline in its serving instantiation (mlp_step.hip INFER:
             # weights in registers from the fragment copies, one barrier per 32-row tile) after the
             # fp32 -> padded bf16 cast
             mod = _native.kernels()
-            if not self._pf_fresh:
-                self._pack_frag()
+            self.frag.ensure_fresh()
             Xb = torch.empty(B, L.in_pad, dtype=torch.bfloat16, device=X.device)
             mod.cast_pad_bf16(X.data_ptr(), B, F, X.stride(0), Xb.data_ptr(), L.in_pad, _native.stream_ptr())
             mod.mlp_step_fwd_infer(Xb.data_ptr(), L.in_pad, self.Pf.data_ptr(), self._w(self.P, "b0").data_ptr(),
@@ -868,11 +534,8 @@ class MLPEngine:
                                    self._w(self.P, "bout").data_ptr(), B, L.num_classes, out.data_ptr(),
                                    pred.data_ptr(), _native.stream_ptr())
             return out, pred
-        _native.kernels().mlp_fwd_infer_f32(X.data_ptr(), X.stride(0), F, L.in_pad, self._w(self.Pb, "W0").data_ptr(),
-                                            self._w(self.P, "b0").data_ptr(), self._w(self.Pb, "W1").data_ptr(),
-                                            self._w(self.P, "b1").data_ptr(), self.dims[-1],
-                                            self._w(self.Pb, "Wout").data_ptr(), self._w(self.P, "bout").data_ptr(),
-                                            B, L.num_classes, out.data_ptr(), pred.data_ptr(), _native.stream_ptr())
+        _native.kernels().mlp_fwd_infer_f32(X.data_ptr(), X.stride(0), F, *self.fused.net, B, L.num_classes,
+                                            out.data_ptr(), pred.data_ptr(), _native.stream_ptr())
         return out, pred
 
     def logits(self, X: torch.Tensor) -> torch.Tensor:
@@ -1008,11 +671,12 @@ class MultilayerPerceptronClassifier(Estimator, ClassifierParams):
         statistics, the class count and the steps per epoch are agreed over the group
         and the gradients are all-reduced every step."""
         dev = X.device
-        K = int(num_classes) if num_classes else int(y.max()) + 1
-        if world_size > 1 and not num_classes:
+        if world_size > 1:
             import torch.distributed as dist
 
             from ..parallel import comm
+        K = int(num_classes) if num_classes else int(y.max()) + 1
+        if world_size > 1 and not num_classes:
             kt = torch.tensor([K], device=dev)
             comm.all_reduce(kt, op=dist.ReduceOp.MAX, group=process_group)
             K = int(kt.item())
@@ -1025,7 +689,6 @@ class MultilayerPerceptronClassifier(Estimator, ClassifierParams):
             s1 = X.double().sum(0)
             s2 = (X.double() ** 2).sum(0)
             if world_size > 1:
-                from ..parallel import comm
                 buf = torch.cat([n, s1, s2])
                 comm.all_reduce(buf, group=process_group)
                 n, s1, s2 = buf[:1], buf[1:1 + X.shape[1]], buf[1 + X.shape[1]:]
@@ -1035,9 +698,6 @@ class MultilayerPerceptronClassifier(Estimator, ClassifierParams):
             X = (X - mean) * inv_std
         B = min(self.blockSize, X.shape[0])
         if world_size > 1:  # every rank must run the same number of steps (collectives!)
-            import torch.distributed as dist
-
-            from ..parallel import comm
             bt = torch.tensor([B], device=dev)
             comm.all_reduce(bt, op=dist.ReduceOp.MIN, group=process_group)
             B = int(bt.item())
@@ -1049,9 +709,6 @@ class MultilayerPerceptronClassifier(Estimator, ClassifierParams):
         global_batch = B * world_size
         steps_per_epoch = max(1, N // B)
         if world_size > 1:
-            import torch.distributed as dist
-
-            from ..parallel import comm
             st = torch.tensor([steps_per_epoch], device=dev)
             comm.all_reduce(st, op=dist.ReduceOp.MIN, group=process_group)
             steps_per_epoch = int(st.item())
@@ -1077,9 +734,8 @@ class MultilayerPerceptronClassifier(Estimator, ClassifierParams):
         # the host is out of the small-batch step loop (batch 256: ~3 launches of ~4 us each per step).
         # (the three-kernel step, or the fused forward + split-K backward of the other H = 128 / 256
         # shapes: both enqueue a fixed kernel sequence with no host read)
-        capturable = eng.native and (eng._plan_ok(Xin[:B], y32[:B]) or (eng.fused_ok and B % 16 == 0))
         use_graph = (eng.native and world_size == 1 and ckpt is None and not os.environ.get("HAR_FAULT_INJECT")
-                     and capturable and os.environ.get("HAR_MLP_EPOCH_GRAPH", "1") != "0"
+                     and eng.graph_ok(Xin[:B], y32[:B]) and os.environ.get("HAR_MLP_EPOCH_GRAPH", "1") != "0"
                      and self.maxIter - start_epoch >= 3)
         n_used = steps_per_epoch * B
         if use_graph:

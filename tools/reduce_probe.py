@@ -35,11 +35,13 @@ def main():
     for nm, rs in (("all", regs), ("bwd slabs", regs[:1]), ("fwd dWout slabs", regs[1:])):
         for mode, mn in ((1 | 4, "reduce+adam"), (1 | 2, "reduce+store")):
             print(f"{nm:18s} {mn:14s} {timed(lambda: run(rs, mode)):7.2f} us   regions={[(a, e, n) for a, e, _, n, _ in rs]}")
-    for S in (1, 4, 16, 64):  # slab-count sweep of the backward region
+    for S in (s for s in (1, 4, 16, 64) if s <= eng.slabs.shape[0]):  # slab-count sweep of the backward region
         r0 = [(regs[0][0], regs[0][1], regs[0][2], S, regs[0][4])]
         print(f"bwd region S={S:<4d}  reduce+adam    {timed(lambda: run(r0, 5)):7.2f} us")
     for S in (1, 16, 64, 256):
         r1 = [(a, e, p, S, ld) for a, e, p, _, ld in regs[1:]]
+        if any(e + (S - 1) * ld > eng.layout.total for _, e, _, _, ld in r1):  # (would read past the buffer)
+            continue
         print(f"Wout region S={S:<4d} reduce+adam    {timed(lambda: run(r1, 5)):7.2f} us")
     print(f"{'adam only':18s} {'':14s} {timed(lambda: run([(0, 4, regs[0][2], 1, 4)], 4)):7.2f} us")
 
