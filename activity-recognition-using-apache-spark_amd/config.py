@@ -72,6 +72,8 @@ class RunConfig:
     hmm: bool = False
     hmm_sequence_col: str = "USER"
     hmm_emission: str = "scaled"             # scaled (p / prior) | posterior
+    hmm_posterior: bool = False              # + forward-backward posteriors of the test predictions (implies hmm)
+    hmm_em_iter: int = 0                     # Baum-Welch iterations on the first classifier's training predictions
     # KMeans + silhouette ClusteringEvaluator (new, opt-in): --kmeans K clusters the training rows' dense
     # numeric features after the classifiers
     kmeans: int = 0
@@ -117,6 +119,8 @@ def build_parser() -> argparse.ArgumentParser:
         elif isinstance(default, list):
             t = float if (default and isinstance(default[0], float)) else (int if default and isinstance(default[0], int) else str)
             ap.add_argument(name, dest=f.name, type=_list(t), default=None)
+        elif f.name == "hmm_em_iter":  # spelled out: "--hmm-em" alone would also abbreviate --hmm-emission
+            ap.add_argument("--hmm-em", name, dest=f.name, type=int, default=None)
         else:
             ap.add_argument(name, dest=f.name, type=type(default) if default is not None else str, default=None)
     return ap
@@ -140,4 +144,6 @@ def config_from_args(argv=None) -> RunConfig:
         v = getattr(a, f.name)
         if v is not None:
             setattr(cfg, f.name, v)
+    if cfg.hmm_posterior or cfg.hmm_em_iter > 0:  # both are switches OF the smoother
+        cfg.hmm = True
     return cfg

@@ -35,6 +35,14 @@ Limits
 
 Because every score is an integer, the max-plus products the kernels form over chunks of steps are
 exact and associative: the parallel decode equals this sequential definition bit for bit, ties included.
+
+Posteriors
+    ``forward_backward_torch`` / ``forward_backward_native`` / ``forward_backward`` (further down) are the
+    same three for the sum-product semiring: fp64 in the probability domain (``emission_likelihoods``,
+    ``transition_probs``, ``start_probs`` turn the integer scores into ``B``, ``P``, ``p0``), giving the
+    state posteriors ``gamma``, the per-sequence log-likelihoods and the summed pairwise posteriors ``xi``
+    of Baum-Welch.  Floating-point sums are not associative, so there the kernels
+    (``csrc/kernels/hmm_fb.hip``) agree with the definition within a derived rounding bound, not bit for bit.
 """
 from __future__ import annotations
 
@@ -210,6 +218,181 @@ def viterbi_native(E: torch.Tensor, A: torch.Tensor, pi: torch.Tensor, seq_offse
 def viterbi(E: torch.Tensor, A: torch.Tensor, pi: torch.Tensor, seq_offsets) -> Tuple[torch.Tensor, torch.Tensor]:
     """(path int32 [T], score int64 [S]); dispatches on ``E``'s device."""
     return viterbi_native(E, A, pi, seq_offsets) if E.is_cuda else viterbi_torch(E, A, pi, seq_offsets)
+
+
+# ------------------------------------------------------------------ posteriors: forward-backward
+# Everything below is fp64 in the PROBABILITY domain: the sum-product semiring (+, x) over positive values
+# replaces Viterbi's (max, +) over integers.  ``forward_backward_torch`` is the CPU path and the oracle of
+# ``csrc/kernels/hmm_fb.hip``.
+#
+# Kernel precondition (documented, never checked by a device read): ``B`` in [2^-93, 1] with a 1 in every
+# row, ``P`` and ``p0`` in [2^-52, 1].  ``emission_likelihoods`` / ``transition_probs`` / ``start_probs``
+# produce such values by construction (e^-64 > 2^-93; e^-32 / K row-normalised stays above 2^-52).
+FB_PHASES = ("flags", "chunk_products", "prefix_scan", "suffix_scan", "chunk_pass", "reductions")
+FB_VARIANTS = {"auto": 0, "lanes": 1, "mfma": 2}   # phase 1 at K > 8: (i, j)-lane LDS kernel | f64 MFMA
+
+
+def emission_likelihoods(E: torch.Tensor) -> torch.Tensor:
+    """fp64 [T, K]: ``exp((E_t(j) - max_j E_t(j)) * 2^-20)`` — every row's maximum is exactly 1 and every
+    entry at least e^-64 (the scores lie in [-2^25, 2^25])."""
+    if E.dim() != 2 or E.dtype != torch.int32:
+        raise ValueError("E must be int32 [T, K]")
+    e = E.long()
+    if e.shape[0] == 0:
+        return torch.empty(e.shape, dtype=torch.float64, device=E.device)
+    return torch.exp((e - e.max(dim=1, keepdim=True).values).double() / Q)
+
+
+def transition_probs(qA: torch.Tensor) -> torch.Tensor:
+    """fp64 [K, K]: ``exp(qA * 2^-20)`` with every row normalised to sum 1."""
+    p = torch.exp(qA.double() / Q)
+    return p / p.sum(dim=1, keepdim=True)
+
+
+def start_probs(qpi: torch.Tensor) -> torch.Tensor:
+    """fp64 [K]: ``exp(qpi * 2^-20)`` normalised to sum 1."""
+    p = torch.exp(qpi.double() / Q)
+    return p / p.sum()
+
+
+def loglik_of_scores(loglik: torch.Tensor, E: torch.Tensor, seq_offsets) -> torch.Tensor:
+    """The log-likelihood under the scores ``E`` themselves: adds back ``2^-20 * sum_t max_j E_t(j)`` per
+    sequence (an exact int64 segment sum) to the ``loglik`` of ``emission_likelihoods(E)``."""
+    T = E.shape[0]
+    off = _host_offsets(seq_offsets, T)
+    if T == 0:
+        return loglik.clone()
+    mx = E.long().max(dim=1).values
+    cs = torch.cat([torch.zeros(1, dtype=torch.int64, device=E.device), torch.cumsum(mx, 0)])
+    off_d = off.to(E.device)
+    return loglik + (cs[off_d[1:]] - cs[off_d[:-1]]).double() / Q
+
+
+def check_fb_args(B: torch.Tensor, P: torch.Tensor, p0: torch.Tensor, seq_offsets) -> torch.Tensor:
+    """Validate shapes, dtypes and limits (``ValueError``); returns the offsets as a host tensor."""
+    if B.dim() != 2 or B.dtype != torch.float64:
+        raise ValueError("B must be fp64 [T, K]")
+    T, K = B.shape
+    if not 1 <= K <= MAX_STATES:
+        raise ValueError(f"forward-backward takes 1..{MAX_STATES} states, got {K}")
+    if T > MAX_STEPS:
+        raise ValueError(f"forward-backward takes fewer than 2^31 steps, got {T}")
+    if P.dtype != torch.float64 or tuple(P.shape) != (K, K):
+        raise ValueError(f"P must be fp64 [{K}, {K}]")
+    if p0.dtype != torch.float64 or tuple(p0.shape) != (K,):
+        raise ValueError(f"p0 must be fp64 [{K}]")
+    return _host_offsets(seq_offsets, T)
+
+
+def _fb_empty(T: int, K: int, S: int, dev, want_xi: bool):
+    return (torch.empty(T, K, dtype=torch.float64, device=dev), torch.empty(S, dtype=torch.float64, device=dev),
+            torch.zeros(K, K, dtype=torch.float64, device=dev) if want_xi else None)
+
+
+def forward_backward_torch(B: torch.Tensor, P: torch.Tensor, p0: torch.Tensor, seq_offsets, want_xi: bool = False):
+    """The sequential scaled recurrences, vectorised ACROSS sequences only (like ``viterbi_torch``).
+
+    ``gamma`` fp64 [T, K]: ``gamma_t(j) = P(s_t = j | the whole sequence)``, every row normalised by its
+    own sum; ``loglik`` fp64 [S]: the log of the sum over all paths; ``xi`` fp64 [K, K] (``want_xi``): the
+    sum over every step t that does not start a sequence of the pairwise posterior of (s_{t-1}, s_t), each
+    step's K x K table normalised by its own sum."""
+    off = check_fb_args(B, P, p0, seq_offsets)
+    T, K = B.shape
+    dev = B.device
+    S = off.numel() - 1
+    gamma, loglik, xi = _fb_empty(T, K, S, dev, want_xi)
+    if T == 0:
+        return gamma, loglik, xi
+    lens = off[1:] - off[:-1]
+    order = torch.argsort(lens, descending=True, stable=True)
+    slen = lens[order]
+    starts = off[:-1][order].to(dev)
+    maxlen = int(slen[0])
+    nact = (S - torch.searchsorted(slen.flip(0).contiguous(), torch.arange(maxlen, dtype=torch.int64), right=True)).tolist()
+    alpha = torch.empty(T, K, dtype=torch.float64, device=dev)      # each row scaled to sum 1
+    a = p0.view(1, K) * B[starts]                                   # [S, K]
+    c = a.sum(1, keepdim=True)
+    a = a / c
+    alpha[starts] = a
+    ll = torch.log(c.squeeze(1))
+    for tau in range(1, maxlen):
+        n = nact[tau]
+        rows = starts[:n] + tau
+        x = (a[:n] @ P) * B[rows]
+        c = x.sum(1, keepdim=True)
+        a[:n] = x / c
+        alpha[rows] = a[:n]
+        ll[:n] += torch.log(c.squeeze(1))
+    loglik[order.to(dev)] = ll
+    beta = torch.ones(S, K, dtype=torch.float64, device=dev)        # any positive scale: gamma and xi normalise
+    for tau in range(maxlen - 1, -1, -1):
+        n = nact[tau]
+        rows = starts[:n] + tau
+        if tau + 1 < maxlen:
+            m = nact[tau + 1]                                       # those with a step tau + 1
+            if m:
+                w = B[rows[:m] + 1] * beta[:m]                      # [m, K] over j
+                if want_xi:
+                    x = alpha[rows[:m]][:, :, None] * P[None, :, :] * w[:, None, :]
+                    xi += (x / x.sum(dim=(1, 2), keepdim=True)).sum(0)
+                nb = w @ P.t()
+                beta[:m] = nb / nb.sum(1, keepdim=True)
+            # a sequence whose last step is tau keeps beta = 1
+        g = alpha[rows] * beta[:n]
+        gamma[rows] = g / g.sum(1, keepdim=True)
+    return gamma, loglik, xi
+
+
+def forward_backward_native(B: torch.Tensor, P: torch.Tensor, p0: torch.Tensor, seq_offsets, want_xi: bool = False,
+                            chunk: Optional[int] = None, out=None, workspace: Optional[torch.Tensor] = None,
+                            phases: Optional[Tuple[int, int]] = None, offsets_device: Optional[torch.Tensor] = None,
+                            variant: str = "auto"):
+    """The HIP forward-backward of device tensors (``csrc/kernels/hmm_fb.hip``).  ``chunk`` overrides the
+    chunk length, ``out`` = (gamma, loglik, xi | None) buffers to fill, ``workspace`` a uint8 scratch tensor
+    to reuse, ``phases`` = (first, last) of ``FB_PHASES`` to run over that workspace, ``variant`` the phase-1
+    kernel at K > 8 (``FB_VARIANTS``)."""
+    off = check_fb_args(B, P, p0, seq_offsets)
+    if not (B.is_cuda and P.is_cuda and p0.is_cuda):
+        raise ValueError("forward_backward_native takes device tensors")
+    if variant not in FB_VARIANTS:
+        raise ValueError(f"unknown variant {variant!r} ({' | '.join(FB_VARIANTS)})")
+    T, K = B.shape
+    S = off.numel() - 1
+    dev = B.device
+    gamma, loglik, xi = out if out is not None else _fb_empty(T, K, S, dev, want_xi)
+    ok = gamma.dtype == torch.float64 and gamma.numel() == T * K and gamma.is_contiguous() \
+        and loglik.dtype == torch.float64 and loglik.numel() == S and loglik.is_contiguous() \
+        and (not want_xi or (xi is not None and xi.dtype == torch.float64 and xi.numel() == K * K and xi.is_contiguous()))
+    if not ok:
+        raise ValueError("out = (fp64 [T, K], fp64 [S], fp64 [K, K] with want_xi) contiguous")
+    if T == 0:
+        return gamma, loglik, (xi if want_xi else None)
+    mod = _native.kernels()
+    L = int(chunk) if chunk is not None else int(mod.hmm_chunk_len())
+    if L < 1:
+        raise ValueError(f"chunk length must be >= 1, got {L}")
+    need = int(mod.hmm_fb_workspace_bytes(T, K, S, L, bool(want_xi)))
+    if need < 0:
+        raise ValueError(f"hmm forward-backward: shape T = {T}, K = {K}, S = {S}, L = {L} is out of range")
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif workspace.dtype != torch.uint8 or workspace.numel() < need or not workspace.is_cuda:
+        raise ValueError(f"workspace must be a device uint8 tensor of >= {need} bytes")
+    B, P, p0 = B.contiguous(), P.contiguous(), p0.contiguous()
+    off_d = offsets_device if offsets_device is not None else off.to(dev)
+    lo, hi = phases if phases is not None else (0, len(FB_PHASES) - 1)
+    mod.hmm_forward_backward(B.data_ptr(), P.data_ptr(), p0.data_ptr(), off_d.data_ptr(), T, K, S, L,
+                             workspace.data_ptr(), workspace.numel(), gamma.data_ptr(), loglik.data_ptr(),
+                             xi.data_ptr() if want_xi else 0, int(lo), int(hi), FB_VARIANTS[variant],
+                             _native.stream_ptr())
+    return gamma, loglik, (xi if want_xi else None)
+
+
+def forward_backward(B: torch.Tensor, P: torch.Tensor, p0: torch.Tensor, seq_offsets, want_xi: bool = False):
+    """(gamma fp64 [T, K], loglik fp64 [S], xi fp64 [K, K] | None); dispatches on ``B``'s device."""
+    if B.is_cuda:
+        return forward_backward_native(B, P, p0, seq_offsets, want_xi)
+    return forward_backward_torch(B, P, p0, seq_offsets, want_xi)
 
 
 # ------------------------------------------------------------------ timelines

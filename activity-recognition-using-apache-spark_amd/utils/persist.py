@@ -139,9 +139,13 @@ def _build(md, t, children, device):
     if cls == "HMMSmootherModel":
         from ..models.hmm import HMMSmootherModel
 
-        return HMMSmootherModel(t["logA"], t["logpi"], t["prior"], st.get("emission", "scaled"),
-                                p.get("sequenceCol", "USER"), p.get("probabilityCol", "probability"),
-                                p.get("outputCol", "smoothedPrediction"), uid=uid, device=_dev(device))
+        m = HMMSmootherModel(t["logA"], t["logpi"], t["prior"], st.get("emission", "scaled"),
+                             p.get("sequenceCol", "USER"), p.get("probabilityCol", "probability"),
+                             p.get("outputCol", "smoothedPrediction"), uid=uid, device=_dev(device))
+        # Baum-Welch's record (absent from models fitted without it, and from older files)
+        m.emIterations = int(st.get("emIterations", 0))
+        m.objectiveHistory = [float(v) for v in st.get("objectiveHistory", [])]
+        return m
     if cls == "MultilayerPerceptronClassificationModel":
         from ..models.mlp import MLPEngine, MultilayerPerceptronClassificationModel
 

@@ -725,6 +725,16 @@ PYBIND11_MODULE(_har_native, m) {
                           L, P<void>(ws), ws_bytes, P<int32_t>(path), P<int64_t>(score), phase_lo, phase_hi, S(st)),
           "hmm_viterbi");
   });
+  m.def("hmm_fb_workspace_bytes", [](int64_t T, int K, int64_t S, int L, bool want_xi) {
+    return har_hmm_fb_workspace_bytes(T, K, S, L, want_xi ? 1 : 0);
+  });
+  m.def("hmm_forward_backward", [](u B, u Pm, u p0, u off, int64_t T, int K, int64_t nseq, int L, u ws, int64_t ws_bytes,
+                                   u gamma, u loglik, u xi, int phase_lo, int phase_hi, int variant, u st) {
+    check(har_hmm_forward_backward(P<const double>(B), P<const double>(Pm), P<const double>(p0), P<const int64_t>(off), T, K,
+                                   nseq, L, P<void>(ws), ws_bytes, P<double>(gamma), P<double>(loglik), P<double>(xi),
+                                   phase_lo, phase_hi, variant, S(st)),
+          "hmm_forward_backward");
+  });
 
   // K-means and the silhouette (kmeans.hip)
   m.def("kmeans_rows_per_block", []() { return har_kmeans_rows_per_block(); });

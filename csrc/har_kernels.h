@@ -524,6 +524,23 @@ int har_hmm_viterbi(const int32_t* E, const int32_t* A, const int32_t* pi, const
                     int64_t S, int L, void* ws, int64_t ws_bytes, int32_t* path, int64_t* score, int phase_lo,
                     int phase_hi, hipStream_t s);
 
+// ---- HMM posteriors (hmm_fb.hip): parallel forward-backward over the same concatenated batch ----
+// B [T][K] emission likelihoods, P [K][K] transition probabilities, p0 [K] start probabilities, all fp64 in the
+// probability domain (the caller's contract: B in [2^-93, 1] with a 1 in every row, P and p0 in [2^-52, 1]) ->
+// gamma [T][K] state posteriors (rows sum to 1), loglik [S] per-sequence log-likelihoods, xi [K][K] the summed
+// pairwise posteriors of every step that does not start a sequence (null = not wanted).  Running products are
+// rescaled by powers of two (exact); no atomics, one writer per output element, two runs bitwise equal.
+// ws = har_hmm_fb_workspace_bytes(T, K, S, L, want_xi) bytes of device scratch (-1 = bad shape).  Phases
+// phase_lo..phase_hi of 0..5 run (0 flags, 1 chunk products, 2 prefix scan, 3 suffix scan, 4 chunk pass,
+// 5 reductions).  variant picks phase 1's kernel at K > 8: 0 = the default, 1 = (i, j) lanes through LDS,
+// 2 = v_mfma_f64_16x16x4_f64.  T = 0 launches nothing.  Contract codes: -2 bad shape (as har_hmm_viterbi; also
+// L * K * 8 bytes above the 64 KiB a workgroup keeps a chunk's alpha rows in, a variant outside 0..2, workspace
+// too small), -4 null pointer.
+int64_t har_hmm_fb_workspace_bytes(int64_t T, int K, int64_t S, int L, int want_xi);
+int har_hmm_forward_backward(const double* B, const double* P, const double* p0, const int64_t* seq_offsets, int64_t T,
+                             int K, int64_t S, int L, void* ws, int64_t ws_bytes, double* gamma, double* loglik,
+                             double* xi, int phase_lo, int phase_hi, int variant, hipStream_t s);
+
 // ---- K-means and the silhouette (kmeans.hip): rows x centres on the fp32 matrix cores ----
 // Working rows X [N][D] fp32 (centred by the caller), operand rows C [K][D] with h [K]: the score is
 // s[n][k] = h[k] - <X[n], C[k]> (assignment: C = centres, h = ||C||^2 / 2; silhouette: C = cluster means,

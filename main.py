@@ -14,6 +14,7 @@ DecisionTree(+CV), RandomForest(+CV) — plus NaiveBayes and an MLP — and writ
     python main.py --preset all-numeric --save-models models/
     python main.py --preset gbt --gbt-max-iter 50    # gradient-boosted trees (K trees per round)
     python main.py --hmm --save-models models/       # + Viterbi-smoothed timeline per classifier (HMMSmoother)
+    python main.py --hmm-posterior --hmm-em 10       # + forward-backward posteriors; Baum-Welch-refined transitions
     python main.py --kmeans 6 --save-models models/  # + KMeans clusters, silhouette, purity against the labels
     python main.py --csv-device                      # CSV parsed + dictionary-encoded by the HIP kernels
     python main.py --report                          # + Results table, charts and index.html (report/)
@@ -211,6 +212,7 @@ def run(cfg: RunConfig, ctx=None) -> dict:
             smoother = hmm_est.fit_labels(torch.as_tensor(train["label"].data.astype(np.int64)),
                                           seq_offsets(0, train.count()), n_classes)
         test_offsets = seq_offsets(1, test.count())
+    em_pending = smoother is not None and cfg.hmm_em_iter > 0
     for name in cfg.classifiers:
         est = make_estimator(name, cfg, dev, n_features, n_classes)
         with timer.phase(f"fit:{name}"), data_parallel(ctx):
@@ -234,6 +236,15 @@ def run(cfg: RunConfig, ctx=None) -> dict:
             r = evaluate_all(y_test, pred, raw_pred, n_classes)
         evaluation_block(log, r)
         hmm_rec = {}
+        if em_pending:  # Baum-Welch on the first fitted classifier's probabilities of the training rows
+            em_pending = False
+            hmm_est.emIter = cfg.hmm_em_iter
+            X_tr = best.features_input(train) if hasattr(best, "features_input") else features_tensor(train, "features", dev)
+            with timer.phase("fit:hmm-em"):
+                smoother = hmm_est.fit_em(smoother, best.predict_all(X_tr)[1], seq_offsets(0, train.count()))
+            h = smoother.objectiveHistory
+            log.print("HMM Baum-Welch on %s: %d iterations, penalised objective %g -> %g"
+                      % (name, smoother.emIterations, h[0], h[-1]))
         if smoother is not None:
             with timer.phase(f"smooth:{name}"):
                 path, _ = smoother.decode(prob, test_offsets)
@@ -243,6 +254,15 @@ def run(cfg: RunConfig, ctx=None) -> dict:
             log.print("HMM smoothed Accuracy = %g  (%d segments, %d before smoothing; %d sequences)"
                       % (hmm_rec["smoothed_accuracy"], hmm_rec["segments"], hmm_rec["raw_segments"],
                          test_offsets.numel() - 1))
+            if cfg.hmm_posterior:
+                from har.ops.hmm import _lowest_argmax
+
+                with timer.phase(f"posterior:{name}"):
+                    gamma, loglik = smoother.posterior(prob, test_offsets)
+                hmm_rec["posterior_accuracy"] = float((_lowest_argmax(gamma, 1)[1] == y_test).double().mean())
+                hmm_rec["posterior_log_likelihood"] = float(loglik.sum())
+                log.print("HMM posterior Accuracy = %g  (log-likelihood %g)"
+                          % (hmm_rec["posterior_accuracy"], hmm_rec["posterior_log_likelihood"]))
         row = (csvout.cv_row if name.endswith("cv") else csvout.plain_row)(str(model), r, train_s, test_s)
         (cv_rows if name.endswith("cv") else plain_rows).append(row)
         records[name] = {"model": str(model), "train_s": train_s, "predict_s": test_s,

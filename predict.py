@@ -19,7 +19,9 @@ Output CSV columns: ``row, UID (if present), prediction, label_name, probability
 predictions of every sequence (runs of equal ``--sequence-col`` values, in row order) with the saved
 HMMSmoother: the CSV gains ``smoothed_prediction, smoothed_label_name``, the JSON record ``smooth_s``,
 ``segments`` (and ``smoothed_accuracy`` for labelled input), and ``--segments-out FILE`` writes the
-timeline ``sequence, first_row, last_row, state, label_name``.
+timeline ``sequence, first_row, last_row, state, label_name``.  ``--smooth hmm-posterior`` labels every
+window with the argmax of its forward-backward posterior instead: the CSV also gains
+``smoothed_confidence`` (that posterior's maximum) and the JSON ``smoothed_log_likelihood``.
 When the input still has the ``ACTIVITY`` column the script also prints the
 reference's evaluation block (accuracy, weighted F1, ...).  Rows whose string
 categories were never seen at training time are rejected by the indexers unless
@@ -71,8 +73,8 @@ def run(args) -> dict:
     model = getattr(model, "bestModel", model)
     smoother = None
     if args.smooth:
-        if args.smooth != "hmm":
-            raise ValueError(f"unknown smoother {args.smooth!r} (hmm)")
+        if args.smooth not in ("hmm", "hmm-posterior"):
+            raise ValueError(f"unknown smoother {args.smooth!r} (hmm | hmm-posterior)")
         smoother = persist.load(os.path.join(args.models, "hmm"), device=dev)
     t0 = time.perf_counter()
     raw = read_csv(args.data, device=dev if (args.csv_device and dev.type == "cuda") else None)
@@ -99,7 +101,7 @@ def run(args) -> dict:
         y = torch.as_tensor(table["label"].data.astype(np.int64), device=dev)
         r = evaluate_all(y, pred, raw_pred, int(raw_pred.shape[1]))
         rec.update({"accuracy": r.accuracy, "f1": r.f1})
-    sp = None
+    sp = conf = None
     if smoother is not None:
         from har.models.hmm import sequence_offsets
         from har.ops.hmm import segments
@@ -109,9 +111,19 @@ def run(args) -> dict:
         offsets = sequence_offsets(raw, args.sequence_col or smoother.sequenceCol)
         device_sync(dev)
         t2 = time.perf_counter()
-        path, _ = smoother.decode(prob, offsets)
+        if args.smooth == "hmm-posterior":  # the smoothed probability of every window; its argmax is the label
+            from har.ops.hmm import _lowest_argmax
+
+            gamma, loglik = smoother.posterior(prob, offsets)
+            top, path = _lowest_argmax(gamma, 1)
+            path = path.to(torch.int32)
+        else:
+            path, _ = smoother.decode(prob, offsets)
         device_sync(dev)
         rec["smooth_s"] = round(time.perf_counter() - t2, 6)
+        if args.smooth == "hmm-posterior":
+            rec["smoothed_log_likelihood"] = float(loglik.sum())
+            conf = top.cpu().numpy()
         segs = segments(path, offsets)
         rec["segments"] = len(segs)
         sp = path.long().cpu().numpy()
@@ -130,12 +142,15 @@ def run(args) -> dict:
         with open(args.out, "w", newline="") as f:
             w = csv.writer(f)
             w.writerow(["row"] + (["UID"] if uid is not None else []) + ["prediction", "label_name", "probability"]
-                       + (["smoothed_prediction", "smoothed_label_name"] if sp is not None else []))
+                       + (["smoothed_prediction", "smoothed_label_name"] if sp is not None else [])
+                       + (["smoothed_confidence"] if conf is not None else []))
             for i in range(n):
                 name = labels[p[i]] if labels and p[i] < len(labels) else ""
                 extra = []
                 if sp is not None:
                     extra = [int(sp[i]), labels[sp[i]] if labels and sp[i] < len(labels) else ""]
+                if conf is not None:
+                    extra.append(float(conf[i]))
                 w.writerow([i] + ([int(uid[i])] if uid is not None else []) + [int(p[i]), name, float(pr[i, p[i]])] + extra)
     return rec
 
@@ -189,7 +204,8 @@ def main(argv=None):
     ap.add_argument("--csv-device", action="store_true", help="parse the CSV with the HIP kernels")
     ap.add_argument("--repeat", type=int, default=1, help="timed prediction passes (throughput)")
     ap.add_argument("--handle-invalid", default="error", choices=["error", "skip", "keep"])
-    ap.add_argument("--smooth", default="", help="hmm: Viterbi-smooth the predictions with <models>/hmm")
+    ap.add_argument("--smooth", default="", help="hmm: Viterbi-smooth the predictions with <models>/hmm; "
+                                                 "hmm-posterior: forward-backward posteriors and their argmax")
     ap.add_argument("--sequence-col", default="", help="column whose runs are the sequences (default: the saved one)")
     ap.add_argument("--segments-out", default="", help="with --smooth: write the timeline's segments to this CSV")
     rec = run(ap.parse_args(argv))
