@@ -885,6 +885,18 @@ __device__ __forceinline__ void qn_finalize(const QnArgs& a, int b, int p, doubl
   if (t == 128 && a.hist) a.hist[(int64_t)a.fin_it * a.B + b] = Fout;
 }
 
+// The slot to load for history index j: j itself when it holds one of the ring's `filled` pairs (the slots
+// head - 1, head - 2, ... mod m), else the newest slot (slot 0 while the history is empty).  Membership is
+// by distance behind head, not j < filled: a ring may be partly filled with head anywhere (head = 5,
+// filled = 7 holds slots 4..0, 9, 8), and j < filled then read slot 0 for the valid slots 8 and 9.
+// Uniform (scalar) arithmetic on kernel arguments.
+__device__ __forceinline__ int qn_ring_slot(const QnArgs& a, int j) {
+  int back = a.head - 1 - j;  // steps behind the newest slot
+  back = back < 0 ? back + a.m : back;
+  const int newest = a.head > 0 ? a.head - 1 : a.m - 1;
+  return (j < a.m && back < a.filled) ? j : (a.filled > 0 ? newest : 0);
+}
+
 // One parameter element's operands for phase 1 (x, g, L1 / L2 weights, the W_eff scale and the
 // m history values), loaded at a clamped (always valid) index so the loads are unconditional: the
 // kernel keeps the next element's loads in flight while it computes the current one, and the
@@ -907,10 +919,10 @@ __device__ __forceinline__ DirElem dir_load(const QnArgs& a, int b, int k, int c
   v.wsc = a.pmask[b * D + e] * (col < a.F ? isd : 1.f);
 #pragma unroll
   for (int j = 0; j < QN_MAX_M; ++j) {
-    // slots not filled yet (j >= filled; the ring fills 0, 1, ... before it wraps) re-read slot 0: the
-    // same lines, so they cost no HBM traffic (the batched CV direction is bandwidth-bound while the
-    // history fills), and their coefficients cS / cY are 0; slots >= m are never valid either
-    const int jj = j < a.filled ? j : 0;
+    // slots that hold no pair of the ring re-read a slot that does: the same lines, so they cost no HBM
+    // traffic (the batched CV direction is bandwidth-bound while the history fills), and their
+    // coefficients cS / cY are 0; slots >= m are never valid either
+    const int jj = qn_ring_slot(a, j);
     v.s[j] = a.S[jj * sstride + b * D + e];
     v.y[j] = a.Y[jj * sstride + b * D + e];
   }
@@ -942,7 +954,8 @@ __device__ __forceinline__ void qn_direction_body(const QnArgs& a, int c, int b,
   const int nel = ccn * a.K;
   const uint32_t cmag = 0xffffffffu / (uint32_t)max(ccn, 1) + 1u;  // i / ccn = umulhi(i, cmag) (i ccn < 2^32)
   const int e0 = threadIdx.x, e1 = nel;
-  auto kof = [&](int i) { return (int)__umulhi((uint32_t)i, cmag); };
+  // (a one-column chunk: the magic number 2^32 wraps to 0 — every element then has k = i, not k = 0)
+  auto kof = [&](int i) { return ccn == 1 ? i : (int)__umulhi((uint32_t)i, cmag); };
   // each thread's first three elements in flight during the prologue + recursion (a refill three ahead),
   // issued AFTER the recursion's operand loads (Gram, rho, P1 totals): a counted wait for those then
   // does not also wait for the 75 element loads behind them
@@ -1176,9 +1189,9 @@ __device__ __forceinline__ UpdElem upd_load(const QnArgs& a, int b, int e) {
   for (int j = 0; j < QN_MAX_M; ++j) {
     v.s[j] = v.y[j] = 0.f;
     // FULLM also loads slot `head` (its OLD pair) and accumulates its P3 sums, which finalize never reads;
-    // unfilled slots re-read slot 0 (cached lines; their dots are never read)
+    // slots outside the ring re-read one inside it (cached lines; their dots are never read)
     if (!a.init && (FULLM || (j < a.m && j != a.head))) {
-      const int jl = j < a.filled ? j : 0;
+      const int jl = qn_ring_slot(a, j);
       v.s[j] = a.S[jl * sstride + o];
       v.y[j] = a.Y[jl * sstride + o];
     }
@@ -1679,7 +1692,7 @@ extern "C" int har_lbfgs_phase(const QnArgs* args, int KP, int phase, hipStream_
   const QnArgs& a = *args;
   if ((KP != 8 && KP != 16) || a.K > KP || a.m < 1 || a.m > QN_MAX_M || a.T < 1 || a.T > QN_MAX_TRIALS ||
       a.D != (int64_t)a.K * (a.F + 1) || a.D >= (1LL << 31) || a.nch != har_qn_chunks(a.D, a.B) || phase < 1 ||
-      phase > 2 || a.head < 0 || a.head >= a.m || a.done == nullptr)
+      phase > 2 || a.head < 0 || a.head >= a.m || a.filled < 0 || a.filled > a.m || a.done == nullptr)
     return -2;
   if (a.B == 0) return 0;
   const bool full = a.m == QN_MAX_M;
