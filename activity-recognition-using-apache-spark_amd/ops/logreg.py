@@ -157,9 +157,9 @@ class LogregDesign:
         [srow[sl], srow[sl + 1])).  The kernel then loads everything a lane needs in one round at
         entry instead of searching the slice's column and reading its offsets (grad stamps,
         profiles/r5/lr_kernel_medians.md).  A column's slices are still summed in order by one lane:
-        the gradient is bitwise the fixed-block one.  Built once per matrix (one host read of
-        col_slice, cached on it); HAR_LR_COLBLK=0 keeps the fixed 256-column blocks."""
-        if os.environ.get("HAR_LR_COLBLK", "1") == "0" or self.device.type != "cuda":
+        the gradient is bitwise that of any other blocking.  Built once per matrix (one host read of
+        col_slice, cached on it); (None, 0, None) off the GPU, where no kernel runs."""
+        if self.device.type != "cuda":
             return None, 0, None
         cached = getattr(self.hm, "_lr_col_blk", None)
         if cached is None or cached[3] != self.SL:
@@ -279,11 +279,6 @@ def _arena(specs, dev, into: dict) -> torch.Tensor:
     return buf
 
 
-# how the last native solve ran: 1 = one persistent cooperative launch, 0 = the launch sequence, 3 = the
-# persistent launch timed out in a grid barrier and the fit was rerun as the sequence (tests)
-LAST_SOLVE_MODE = -1
-
-
 class DeviceLogregSolver:
     """Runs ``optim.lbfgs.minimize_trials``' algorithm for the LR objective entirely with the
     logreg_qn.hip kernels: 4 launches per iteration (direction + trials, evaluate, gradient,
@@ -369,8 +364,8 @@ class DeviceLogregSolver:
                 "hist": p(self.hist), "done": p(self.done), "c1": float(self.c1), "tol": float(self.tol)}
 
     def _eval_args(self, tstride: int):
-        """Per launch chunk: positional arguments (but the stream) of the evaluate + gradient
-        launches, built once per tstride: the buffers never move during a solve."""
+        """Per launch chunk: the argument tuples of the evaluate + gradient launches (field order:
+        bind.cpp eval_args / grad_args), built once per tstride: the buffers never move during a solve."""
         cache = self.__dict__.setdefault("_eval_arg_cache", {})
         if tstride not in cache:
             d = self.d
@@ -399,8 +394,8 @@ class DeviceLogregSolver:
         mod = _native.kernels()
         s = _native.stream_ptr()
         for ev, gr in self._eval_args(tstride):
-            mod.logreg_eval(*ev, s)
-            mod.logreg_grad(*gr, s)
+            mod.logreg_eval(ev, s)
+            mod.logreg_grad(gr, s)
         if self.allreduce is not None:
             # data parallel: ONE fp32 all-reduce of [gradients | fixed-point losses], then the exact
             # loss sums back to fp64 (every rank then takes the identical optimizer step)
@@ -446,24 +441,7 @@ class DeviceLogregSolver:
             if plan is None:
                 chunks = lambda ts: [mod.logreg_eval_chunk(ev, gr) for ev, gr in self._eval_args(ts)]  # noqa: E731
                 plan = self._solve_plan = mod.logreg_solve_plan(qa, chunks(self.T), chunks(1), KP)
-            # the launch sequence, or (HAR_LR_PERSISTENT=1) one cooperative launch for the whole solve
-            # (logreg_solve_persistent_kernel, bitwise the same; measured slower); 1 = persistent ran
-            global LAST_SOLVE_MODE
-            self.solve_mode = LAST_SOLVE_MODE = mod.logreg_solve(plan, self.max_iter, self.m, s)
-            if self.solve_mode == 2:
-                # a grid barrier of the persistent solve timed out (its blocks went on unsynchronized):
-                # the results are garbage — rerun the whole fit as the launch sequence, loudly
-                import warnings
-
-                warnings.warn("persistent LR solve: grid barrier timed out; rerunning as the launch sequence")
-                self.reset()
-                self.x.copy_(x0.reshape(self.B, self.D))
-                old = mod.logreg_set_persistent(0)
-                try:
-                    mod.logreg_solve(plan, self.max_iter, self.m, s)
-                finally:
-                    mod.logreg_set_persistent(old)
-                self.solve_mode = LAST_SOLVE_MODE = 3  # 3 = timed out, rerun as the sequence
+            mod.logreg_solve(plan, self.max_iter, self.m, s)
             self.n_evals += 1 + self.max_iter
             return self.x, self.fobj, self.iters
         phase(1, init=1)
@@ -519,8 +497,8 @@ def logreg_margins_native(hm, W_models: torch.Tensor, K: int, n_models: int) -> 
     cat = hm.cat if C else torch.zeros(max(1, N), 1, dtype=torch.int32, device=dev)
     out = torch.empty(n_models, max(1, N), KP, device=dev)
     ones = torch.ones(1, device=dev)
-    mod.logreg_eval(dense.data_ptr(), dense.stride(0), Fd, dcols.data_ptr(), cat.data_ptr(), C, 0, 0, ones.data_ptr(),
-                    W_models.contiguous().data_ptr(), N, F, K, 1, 1, 0, 1, out.data_ptr(), 0, KP, n_models, s)
+    mod.logreg_eval((dense.data_ptr(), dense.stride(0), Fd, dcols.data_ptr(), cat.data_ptr(), C, 0, 0, ones.data_ptr(),
+                     W_models.contiguous().data_ptr(), N, F, K, 1, 1, 0, 1, out.data_ptr(), 0, KP, n_models), s)
     return out[:, :N]
 
 

@@ -158,6 +158,71 @@ struct QnArgsHolder {
   QnArgs a;
 };
 
+// The evaluate / gradient launches' arguments as ops/logreg.py holds them: one tuple per launch, in
+// the order below, ending (evaluate) or followed (gradient: before the column blocks) by KP and the
+// number of models.  Every entry point converts through these two.
+static LogregEvalArgs eval_args(py::tuple e, int& KP, int& n_models) {
+  if (e.size() != 21) throw std::runtime_error("logreg evaluate arguments: 21 fields expected");
+  auto U = [&](int i) { return e[i].cast<u>(); };
+  auto I = [&](int i) { return e[i].cast<int64_t>(); };
+  LogregEvalArgs a;
+  a.dense = P<const float>(U(0));
+  a.ldd = I(1);
+  a.Fd = (int)I(2);
+  a.dense_cols = P<const int32_t>(U(3));
+  a.cat = P<const int32_t>(U(4));
+  a.C = (int)I(5);
+  a.y = P<const int32_t>(U(6));
+  a.rw = P<const float>(U(7));
+  a.inv_wsum = P<const float>(U(8));
+  a.W = P<const float>(U(9));
+  a.N = I(10);
+  a.F = (int)I(11);
+  a.K = (int)I(12);
+  a.T = (int)I(13);
+  a.tstride = (int)I(14);
+  a.model0 = (int)I(15);
+  a.mode = (int)I(16);
+  a.R = P<float>(U(17));
+  a.slab = P<float>(U(18));
+  KP = (int)I(19);
+  n_models = (int)I(20);
+  return a;
+}
+
+static LogregGradArgs grad_args(py::tuple g, int& KP, int& n_models) {
+  if (g.size() != 25) throw std::runtime_error("logreg gradient arguments: 25 fields expected");
+  auto U = [&](int i) { return g[i].cast<u>(); };
+  auto I = [&](int i) { return g[i].cast<int64_t>(); };
+  LogregGradArgs a;
+  a.slab = P<const float>(U(0));
+  a.R = P<const float>(U(1));
+  a.col_map = P<const int32_t>(U(2));
+  a.csc_rows = P<const int32_t>(U(3));
+  a.csc_off = P<const int32_t>(U(4));
+  a.col_slice = P<const int32_t>(U(5));
+  a.SL = (int)I(6);
+  a.inv_std = P<const float>(U(7));
+  a.pmask = P<const float>(U(8));
+  a.N = I(9);
+  a.F = (int)I(10);
+  a.Fd = (int)I(11);
+  a.K = (int)I(12);
+  a.T = (int)I(13);
+  a.tstride = (int)I(14);
+  a.model0 = (int)I(15);
+  a.ntiles = (int)I(16);
+  a.G = P<float>(U(17));
+  a.loss = P<double>(U(18));
+  a.loss_fx = P<float>(U(19));
+  KP = (int)I(20);
+  n_models = (int)I(21);
+  a.col_blk = P<const int32_t>(U(22));
+  a.nblk = (int)I(23);
+  a.srow = P<const int32_t>(U(24));
+  return a;
+}
+
 // One launch chunk of a LogisticRegression objective evaluation: the evaluate + gradient kernels'
 // arguments (pointers fixed for the life of a DeviceLogregSolver).
 struct LogregEvalChunk {
@@ -173,54 +238,9 @@ struct LogregSolvePlan {
   QnArgs q;
   std::vector<LogregEvalChunk> evT, ev1;  // evaluations of the T trials (first) / 1 per model
   int KP = 8;
-  // the persistent solve's barrier counter + timeout flag (2 device words, allocated on first use)
-  std::shared_ptr<uint32_t> sync;
-  int last_mode = 0;  // 1 = the last solve ran persistent, 0 = as the launch sequence
 };
 
-// HAR_LR_PERSISTENT: 0 (default) = the launch sequence, 1 = one cooperative launch when every phase's
-// workgroups are co-resident in one round, 2 = one cooperative launch whenever possible.  Measured
-// (profiles/r4/lr_persistent.md): the persistent solve is bitwise the sequence but SLOWER on MI355X —
-// 1.46 ms vs 1.36 ms of solve kernels for the WISDM fit — back-to-back dependent launches cost less
-// than a grid barrier (release fence + counter + acquire fence), so the phases' own latency chains,
-// not kernel boundaries, bound an iteration
-static int g_lr_persistent = [] {
-  const char* e = std::getenv("HAR_LR_PERSISTENT");
-  return e ? std::atoi(e) : 0;
-}();
-static int lr_persistent_mode() { return g_lr_persistent; }
-
-static bool logreg_solve_persistent(LogregSolvePlan& p, int max_iter, hipStream_t s) {
-  const int mode = lr_persistent_mode();
-  if (mode == 0 || p.evT.size() != 1 || p.ev1.size() != 1) return false;
-  if (!p.sync) {
-    void* d = nullptr;
-    if (hipMalloc(&d, 2 * sizeof(uint32_t)) != hipSuccess) return false;
-    p.sync = std::shared_ptr<uint32_t>(static_cast<uint32_t*>(d), [](uint32_t* q) { (void)hipFree(q); });
-  }
-  const LogregEvalChunk &cT = p.evT[0], &c1 = p.ev1[0];
-  // mode 1: only when the widest phase fits one co-resident round (max_grid = 0: the launcher caps
-  // the grid at the co-resident count; a wider phase then loops, which the batched CV fits lose on)
-  const int rc = har_logreg_solve_persistent(&p.q, &cT.ev, &cT.gr, cT.n_models, &c1.ev, &c1.gr, c1.n_models, p.KP,
-                                             max_iter, p.sync.get(), mode == 1 ? -1 : 0, s);
-  if (rc == -2) throw std::runtime_error("logreg_solve_persistent: invalid arguments");
-  return rc == 0;
-}
-
-// last_mode: 1 = the persistent solve ran and completed, 2 = it ran but a grid barrier timed out
-// (sync[1] set: blocks went on with unsynchronized x / g / history, so the results are garbage and
-// the caller must rerun the fit as the launch sequence — ops/logreg.py does), 0 = the sequence ran
 static void logreg_solve_run(LogregSolvePlan& p, int max_iter, int m, hipStream_t s) {
-  if (logreg_solve_persistent(p, max_iter, s)) {
-    uint32_t flag = 0;  // one blocking 4-byte read: only the opt-in persistent mode pays it
-    check(hipMemcpyAsync(&flag, p.sync.get() + 1, sizeof flag, hipMemcpyDeviceToHost, s) == hipSuccess &&
-                  hipStreamSynchronize(s) == hipSuccess
-              ? 0 : -1,
-          "logreg_solve flag read");
-    p.last_mode = flag ? 2 : 1;
-    return;
-  }
-  p.last_mode = 0;
   auto phase = [&](int ph, int head, int filled, int init, int fin_it) {
     QnArgs a = p.q;
     a.head = head;
@@ -325,84 +345,19 @@ PYBIND11_MODULE(_har_native, m) {
   });
 
   m.def("logreg_eval_tiles", &har_logreg_eval_tiles);
-  m.def("logreg_eval", [](u dense, int64_t ldd, int Fd, u dense_cols, u cat, int C, u y, u rw, u inv_wsum, u W,
-                          int64_t N, int F, int K, int T, int tstride, int model0, int mode, u R, u slab, int KP,
-                          int n_models,
-                          u stream) {
-    LogregEvalArgs a;
-    a.dense = P<const float>(dense);
-    a.ldd = ldd;
-    a.Fd = Fd;
-    a.dense_cols = P<const int32_t>(dense_cols);
-    a.cat = P<const int32_t>(cat);
-    a.C = C;
-    a.y = P<const int32_t>(y);
-    a.rw = P<const float>(rw);
-    a.inv_wsum = P<const float>(inv_wsum);
-    a.W = P<const float>(W);
-    a.N = N;
-    a.F = F;
-    a.K = K;
-    a.T = T;
-    a.tstride = tstride;
-    a.model0 = model0;
-    a.mode = mode;
-    a.R = P<float>(R);
-    a.slab = P<float>(slab);
+  m.def("logreg_eval", [](py::tuple e, u stream) {
+    int KP, n_models;
+    const LogregEvalArgs a = eval_args(e, KP, n_models);
     check(har_logreg_eval(&a, KP, n_models, S(stream)), "logreg_eval");
   });
-  // argument holders for logreg_solve_plan: the same positional arguments as logreg_eval /
-  // logreg_grad below, without the stream
+  // argument holder for logreg_solve_plan: one launch chunk's evaluate + gradient tuples
   py::class_<LogregEvalChunk>(m, "LogregEvalChunk");
   m.def("logreg_eval_chunk", [](py::tuple e, py::tuple g) {
     LogregEvalChunk c{};
-    auto U = [](py::handle h) { return h.cast<u>(); };
-    auto I = [](py::handle h) { return h.cast<int64_t>(); };
-    c.ev.dense = P<const float>(U(e[0]));
-    c.ev.ldd = I(e[1]);
-    c.ev.Fd = (int)I(e[2]);
-    c.ev.dense_cols = P<const int32_t>(U(e[3]));
-    c.ev.cat = P<const int32_t>(U(e[4]));
-    c.ev.C = (int)I(e[5]);
-    c.ev.y = P<const int32_t>(U(e[6]));
-    c.ev.rw = P<const float>(U(e[7]));
-    c.ev.inv_wsum = P<const float>(U(e[8]));
-    c.ev.W = P<const float>(U(e[9]));
-    c.ev.N = I(e[10]);
-    c.ev.F = (int)I(e[11]);
-    c.ev.K = (int)I(e[12]);
-    c.ev.T = (int)I(e[13]);
-    c.ev.tstride = (int)I(e[14]);
-    c.ev.model0 = (int)I(e[15]);
-    c.ev.mode = (int)I(e[16]);
-    c.ev.R = P<float>(U(e[17]));
-    c.ev.slab = P<float>(U(e[18]));
-    c.KP = (int)I(e[19]);
-    c.n_models = (int)I(e[20]);
-    c.gr.slab = P<const float>(U(g[0]));
-    c.gr.R = P<const float>(U(g[1]));
-    c.gr.col_map = P<const int32_t>(U(g[2]));
-    c.gr.csc_rows = P<const int32_t>(U(g[3]));
-    c.gr.csc_off = P<const int32_t>(U(g[4]));
-    c.gr.col_slice = P<const int32_t>(U(g[5]));
-    c.gr.SL = (int)I(g[6]);
-    c.gr.inv_std = P<const float>(U(g[7]));
-    c.gr.pmask = P<const float>(U(g[8]));
-    c.gr.N = I(g[9]);
-    c.gr.F = (int)I(g[10]);
-    c.gr.Fd = (int)I(g[11]);
-    c.gr.K = (int)I(g[12]);
-    c.gr.T = (int)I(g[13]);
-    c.gr.tstride = (int)I(g[14]);
-    c.gr.model0 = (int)I(g[15]);
-    c.gr.ntiles = (int)I(g[16]);
-    c.gr.G = P<float>(U(g[17]));
-    c.gr.loss = P<double>(U(g[18]));
-    c.gr.loss_fx = P<float>(U(g[19]));
-    if ((int)I(g[20]) != c.KP || (int)I(g[21]) != c.n_models) throw std::runtime_error("logreg_eval_chunk: KP / n mismatch");
-    c.gr.col_blk = P<const int32_t>(U(g[22]));
-    c.gr.nblk = (int)I(g[23]);
-    c.gr.srow = P<const int32_t>(U(g[24]));
+    int KP, n_models;
+    c.ev = eval_args(e, c.KP, c.n_models);
+    c.gr = grad_args(g, KP, n_models);
+    if (KP != c.KP || n_models != c.n_models) throw std::runtime_error("logreg_eval_chunk: KP / n mismatch");
     return c;
   });
   py::class_<LogregSolvePlan>(m, "LogregSolvePlan");
@@ -417,52 +372,14 @@ PYBIND11_MODULE(_har_native, m) {
   });
   m.def("logreg_solve", [](LogregSolvePlan& p, int max_iter, int m, u stream) {
     logreg_solve_run(p, max_iter, m, S(stream));
-    return p.last_mode;
   });
-  m.def("logreg_set_persistent", [](int mode) {
-    const int old = g_lr_persistent;
-    g_lr_persistent = mode;
-    return old;
-  });
-  m.def("logreg_set_spin_limit", [](uint32_t n) { return har_logreg_set_spin_limit(n); });
   m.def("lr_set_stamps", [](uint64_t ev, uint64_t dir, uint64_t upd, uint64_t grd) {
     har_lr_set_stamps(reinterpret_cast<uint64_t*>(ev), reinterpret_cast<uint64_t*>(dir), reinterpret_cast<uint64_t*>(upd),
                       reinterpret_cast<uint64_t*>(grd));
   });
-  // the persistent solve's timeout flag (blocking 4-byte read; tests / diagnostics)
-  m.def("logreg_solve_flag", [](const LogregSolvePlan& p) {
-    uint32_t f = 0;
-    if (p.sync) check(hipMemcpy(&f, p.sync.get() + 1, sizeof f, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1,
-                      "logreg_solve_flag");
-    return (int)f;
-  });
-  m.def("logreg_grad", [](u slab, u R, u col_map, u csc_rows, u csc_off, u col_slice, int SL, u inv_std, u pmask,
-                          int64_t N, int F, int Fd, int K, int T, int tstride, int model0, int ntiles, u G, u loss,
-                          u loss_fx, int KP, int n_models, u col_blk, int nblk, u srow, u stream) {
-    LogregGradArgs a;
-    a.col_blk = P<const int32_t>(col_blk);
-    a.nblk = nblk;
-    a.srow = P<const int32_t>(srow);
-    a.slab = P<const float>(slab);
-    a.R = P<const float>(R);
-    a.col_map = P<const int32_t>(col_map);
-    a.csc_rows = P<const int32_t>(csc_rows);
-    a.csc_off = P<const int32_t>(csc_off);
-    a.col_slice = P<const int32_t>(col_slice);
-    a.SL = SL;
-    a.inv_std = P<const float>(inv_std);
-    a.pmask = P<const float>(pmask);
-    a.N = N;
-    a.F = F;
-    a.Fd = Fd;
-    a.K = K;
-    a.T = T;
-    a.tstride = tstride;
-    a.model0 = model0;
-    a.ntiles = ntiles;
-    a.G = P<float>(G);
-    a.loss = P<double>(loss);
-    a.loss_fx = P<float>(loss_fx);
+  m.def("logreg_grad", [](py::tuple g, u stream) {
+    int KP, n_models;
+    const LogregGradArgs a = grad_args(g, KP, n_models);
     check(har_logreg_grad(&a, KP, n_models, S(stream)), "logreg_grad");
   });
   m.def("logreg_col_slices", [](u csc_off, int F, int SL, u col_slice, u stream) {

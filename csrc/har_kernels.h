@@ -243,8 +243,8 @@ typedef struct LogregGradArgs {
   double* loss;             // [n_trial_models] (loss_fx == null)
   float* loss_fx;           // [n_trial_models][5] fixed-point loss pieces for the DP bucket, or null
   const int32_t* col_blk;   // [nblk][4] column blocks (c0, c1, first slice, end slice): <= 256 columns and
-  int nblk;                 // <= 256 slices each (a lone heavier column excepted), or null: fixed 256 columns
-  const int32_t* srow;      // [slices + 1] first CSC row of every slice (with col_blk)
+  int nblk;                 // <= 256 slices each (a lone heavier column excepted); grid.x of the launch
+  const int32_t* srow;      // [slices + 1] first CSC row of every slice
 } LogregGradArgs;
 
 typedef struct QnArgs {
@@ -327,14 +327,8 @@ int har_logreg_col_slices(const int32_t* csc_off, int F, int SL, int32_t* col_sl
 int har_logreg_loss_decode(const float* fx, double* loss, int n, hipStream_t s);
 int har_qn_chunks(int64_t D, int B);
 int har_lbfgs_phase(const QnArgs* a, int KP, int phase, hipStream_t s);
-// the whole L-BFGS / OWL-QN solve as one cooperative launch: 0 ran, -4 not available here (use
-// the launch sequence), -2 invalid; sync = 2 device words (barrier counter, timeout flag)
-uint32_t har_logreg_set_spin_limit(uint32_t n);
 // diagnostic phase stamps of the evaluation / direction / update kernels (tools/lr_stamps.py); null = off
 void har_lr_set_stamps(uint64_t* ev, uint64_t* dir, uint64_t* upd, uint64_t* grd);
-int har_logreg_solve_persistent(const QnArgs* q, const LogregEvalArgs* evT, const LogregGradArgs* grT, int nT,
-                                const LogregEvalArgs* ev1, const LogregGradArgs* gr1, int n1, int KP, int max_iter,
-                                uint32_t* sync, int max_grid, hipStream_t s);
 
 
 

@@ -28,6 +28,9 @@
 // A one-hot feature of the reference's 3,100-dim encoding (Main/main.py:51-66) is one gathered
 // weight column per row instead of 3,090 multiplications by zero: the WISDM objective reads
 // ~60 bytes per row instead of 12.4 KB.
+//
+// A fit is this launch sequence; the whole solve as one cooperative launch with grid barriers measured
+// slower and was removed (profiles/r4/lr_persistent.md).
 #include <algorithm>
 #include <cstdlib>
 
@@ -59,43 +62,39 @@ constexpr int EVAL_ROWS = 256;
 // chunks newest-first (the last one is still in LDS) for the tile's dense gradient R^T X.
 // ---------------------------------------------------------------------------------------------
 constexpr int EVAL_DCH = 32;                       // dense columns per LDS chunk
-// LDS row stride of the dense tile (a compile-time constant: the tile's row addresses fold into
-// immediate offsets): 33 in general, 11 for designs of at most 10 dense columns (the reference
-// encoding) — an 11 KB tile instead of 34 KB, so three times as many evaluation workgroups fit a CU
-// (the 54-model CrossValidator batch: 62 -> 49 us per evaluation)
-constexpr int EVAL_XLD_NARROW = 11;
-__host__ __device__ constexpr int eval_xld(int Fd) { return Fd <= EVAL_XLD_NARROW - 1 ? EVAL_XLD_NARROW : EVAL_DCH + 1; }
-// Dense designs wider than the narrow tile run both dense products on the matrix cores (MF kernels,
-// v_mfma_f32_16x16x4_f32: fp32 operands, fp32 accumulation): the margins of the tile's 256 rows as
-// W^T . X^T (16 classes x 4 columns per step; KP = 8 pads the class rows with zeros) and the tile's
-// dense gradient R^T . X (16 classes x 16 columns, the rows split over the 4 waves, their partials
-// added in a fixed order: still bitwise reproducible).  Row pitch 36: the chunk zero-padded to a
-// multiple of 4 columns, and the 16 rows x 4 columns of an operand read hit 64 distinct banks.
+// Both dense products run on the matrix cores (v_mfma_f32_16x16x4_f32: fp32 operands, fp32
+// accumulation): the margins of the tile's 256 rows as W^T . X^T (16 classes x 4 columns per step;
+// KP = 8 pads the class rows with zeros) and the tile's dense gradient R^T . X (16 classes x 16
+// columns, the rows split over the 4 waves, their partials added in a fixed order: still bitwise
+// reproducible).  The LDS row pitch of the dense tile is a compile-time constant (the tile's row
+// addresses fold into immediate offsets), one of two:
+//   wide, 36: the chunk zero-padded to a multiple of 4 columns, and the 16 rows x 4 columns of an
+//     operand read hit 64 distinct banks (profiles/r4/lr_dense_mfma.md);
+//   narrow, 12, for designs of at most EVAL_NARROW_FD dense columns (the reference encoding): a 12 KB
+//     tile instead of 36 KB, so three times as many evaluation workgroups fit a CU (the 54-model
+//     CrossValidator batch: 62 -> 49 us per evaluation), the chunk padded to 12 columns (a pass-A
+//     operand read still hits 64 distinct banks) and staged by row-owning threads.
+// The scalar products these replaced (pass B: 80 256-long LDS chains, ~5.3k cycles, against 16 MFMAs
+// per wave: 4.7k -> 2.5k cycles) lost the same-box A/B for the single fit and the CrossValidator
+// batch alike: LR 0.93 vs 0.94-0.99 ms, LR-CV 4.28-4.34 vs 4.36-4.60 ms (profiles/r5/lr_grad_blocks.md).
+constexpr int EVAL_NARROW_FD = 10;
 constexpr int EVAL_XLD_MF = 36;
-// ... and the narrow designs (<= 10 dense columns, the reference encoding) on the matrix cores too, at
-// row pitch 12 (the chunk padded to 12 columns; 16 rows x 4 columns of a pass-A operand read still hit
-// 64 distinct banks): pass B's 80 scalar 256-long LDS chains (~5.3k cycles, eval stamps) become 16
-// MFMAs per wave (4.7k -> 2.5k cycles).  With the row-owned staging of the narrow tile it is the default
-// for both the single fit and the 54-model CrossValidator batch (same-box A/B: LR 0.93 vs 0.94-0.99 ms,
-// LR-CV 4.28-4.34 vs 4.36-4.60 ms, profiles/r5/lr_grad_blocks.md); HAR_LR_EVAL_MFN=0 keeps the scalar
-// narrow kernel, -1 uses the MFMA one for launches of <= 256 workgroups only
 constexpr int EVAL_XLD_MFN = 12;
-template <int XLD> constexpr bool eval_mf() { return XLD == EVAL_XLD_MF || XLD == EVAL_XLD_MFN; }
 
 template <int KP, int XLD>
 __device__ __forceinline__ void eval_stage_chunk(const LogregEvalArgs& a, const float* W, float* wd, float* xs,
                                                  int c0, int nc, int64_t r0, int64_t nrow_tile, bool weights) {
   const int tid = threadIdx.x;
-  // (MF pitch: columns nc .. nc4 - 1 of the chunk staged as zeros, the MFMA k steps are 4 wide)
-  const int ncs = eval_mf<XLD>() ? (nc + 3) & ~3 : nc;
+  // (columns nc .. ncs - 1 of the chunk staged as zeros, the MFMA k steps are 4 wide)
+  const int ncs = (nc + 3) & ~3;
   if (weights)
     for (int e = tid; e < ncs * KP; e += EVAL_ROWS)
       wd[e] = e / KP < nc ? W[(int64_t)a.dense_cols[c0 + e / KP] * KP + (e % KP)] : 0.f;
-  if constexpr (XLD == EVAL_XLD_NARROW || XLD == EVAL_XLD_MFN) {
+  if constexpr (XLD == EVAL_XLD_MFN) {
     // narrow tile (<= 10 columns): thread = row, its nc values in ONE round of loads (the flat loop
     // below takes two rounds of 8 for the 10 x 256 tile, with an integer division per element);
-    // the MFMA pitch's columns nc .. ncs - 1 as zeros
-    constexpr int NW = EVAL_XLD_NARROW - 1;
+    // the columns nc .. ncs - 1 as zeros
+    constexpr int NW = EVAL_NARROW_FD;
     const bool in = tid < nrow_tile;
     const float* rp = a.dense + (r0 + (in ? tid : 0)) * a.ldd + c0;
     float v[NW];
@@ -133,24 +132,21 @@ __device__ __forceinline__ f32x4_t mfma4(float a, float b, f32x4_t c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
-// The kernel bodies below take their workgroup coordinates as arguments: the stand-alone kernels pass
-// blockIdx / gridDim, the persistent solve (logreg_solve_persistent_kernel) its virtual blocks.
 template <int KP, int XLD, bool STAMP = false>
-__device__ __forceinline__ void logreg_eval_body(const LogregEvalArgs& a, int bx, int by, int gdx, float* smem,
-                                                 uint64_t* st = nullptr) {
+__global__ __launch_bounds__(EVAL_ROWS) void logreg_eval_kernel(LogregEvalArgs a, uint64_t* st) {
+  extern __shared__ float smem[];
   HAR_LR_STAMP(0)
   const int Fd = a.Fd;
   float* wd = smem;                                // [EVAL_DCH][KP] dense weights of the chunk
-  constexpr int xld = XLD;
-  float* xs = wd + EVAL_DCH * KP;                  // [EVAL_ROWS][xld] dense row tile, one chunk
-  float* rs = xs + EVAL_ROWS * xld;                // [EVAL_ROWS][KP]
+  float* xs = wd + EVAL_DCH * KP;                  // [EVAL_ROWS][XLD] dense row tile, one chunk
+  float* rs = xs + EVAL_ROWS * XLD;                // [EVAL_ROWS][KP]
   float* red = rs + EVAL_ROWS * KP;                // [EVAL_ROWS / 64]
-  constexpr bool MF = eval_mf<XLD>();              // matrix-core dense products
-  float* pb = red + EVAL_ROWS / 64;                // MF: [4 waves][EVAL_DCH][KP] gradient partials
+  float* pb = red + EVAL_ROWS / 64;                // [4 waves][EVAL_DCH][KP] gradient partials
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int l16 = lane & 15, kq = lane >> 4;
 
   const int tid = threadIdx.x;
+  const int bx = blockIdx.x, by = blockIdx.y;      // (row tile, trial slot of the launch)
   const int bt = a.model0 + by * a.tstride;  // trial model (its residual rows: R slot by)
   const int s = bt / a.T;                          // spec (row-weight vector) of the model
   const int64_t r0 = (int64_t)bx * EVAL_ROWS;
@@ -185,40 +181,31 @@ __device__ __forceinline__ void logreg_eval_body(const LogregEvalArgs& a, int bx
 #pragma unroll
   for (int k = 0; k < KP; ++k) z[k] = W[(int64_t)a.F * KP + k];  // intercept row
   f32x4_t za[4] = {f32x4_t{0.f, 0.f, 0.f, 0.f}, f32x4_t{0.f, 0.f, 0.f, 0.f}, f32x4_t{0.f, 0.f, 0.f, 0.f},
-                   f32x4_t{0.f, 0.f, 0.f, 0.f}};  // MF: z^T of the wave's 4 row blocks (lane: row l16, classes 4 kq + r)
+                   f32x4_t{0.f, 0.f, 0.f, 0.f}};  // z^T of the wave's 4 row blocks (lane: row l16, classes 4 kq + r)
   for (int ch = 0; ch < nchunk; ++ch) {
     const int c0 = ch * EVAL_DCH, nc = min(EVAL_DCH, Fd - c0);
     if (ch) __syncthreads();                       // the previous chunk is consumed
     eval_stage_chunk<KP, XLD>(a, W, wd, xs, c0, nc, r0, nrow_tile, true);
     __syncthreads();
-    if constexpr (MF) {
-      const int nc4 = (nc + 3) & ~3;
-      for (int j0 = 0; j0 < nc4; j0 += 4) {
-        const float av = l16 < KP ? wd[(j0 + kq) * KP + l16] : 0.f;  // A = W^T [class l16][column j0 + kq]
+    const int nc4 = (nc + 3) & ~3;
+    for (int j0 = 0; j0 < nc4; j0 += 4) {
+      const float av = l16 < KP ? wd[(j0 + kq) * KP + l16] : 0.f;  // A = W^T [class l16][column j0 + kq]
 #pragma unroll
-        for (int rb = 0; rb < 4; ++rb)                                   // B = X^T [column j0 + kq][row l16]
-          za[rb] = mfma4(av, xs[(wv * 64 + rb * 16 + l16) * XLD + j0 + kq], za[rb]);
-      }
-    } else if (ok) {
-      for (int j = 0; j < nc; ++j) {
-        const float xv = xs[tid * xld + j];
-#pragma unroll
-        for (int k = 0; k < KP; ++k) z[k] = fmaf(xv, wd[j * KP + k], z[k]);
-      }
+      for (int rb = 0; rb < 4; ++rb)                                   // B = X^T [column j0 + kq][row l16]
+        za[rb] = mfma4(av, xs[(wv * 64 + rb * 16 + l16) * XLD + j0 + kq], za[rb]);
     }
   }
   HAR_LR_STAMP(1)
-  if constexpr (MF) {  // the margins through LDS to their rows' threads
+  // the margins through LDS to their rows' threads
 #pragma unroll
-    for (int rb = 0; rb < 4; ++rb)
+  for (int rb = 0; rb < 4; ++rb)
 #pragma unroll
-      for (int r = 0; r < 4; ++r)
-        if (4 * kq + r < KP) rs[(wv * 64 + rb * 16 + l16) * KP + 4 * kq + r] = za[rb][r];
-    __syncthreads();
+    for (int r = 0; r < 4; ++r)
+      if (4 * kq + r < KP) rs[(wv * 64 + rb * 16 + l16) * KP + 4 * kq + r] = za[rb][r];
+  __syncthreads();
 #pragma unroll
-    for (int k = 0; k < KP; ++k) z[k] += rs[tid * KP + k];
-    __syncthreads();                               // rs is rewritten with the residuals below
-  }
+  for (int k = 0; k < KP; ++k) z[k] += rs[tid * KP + k];
+  __syncthreads();                                 // rs is rewritten with the residuals below
   float lossv = 0.f;
   if (ok) {
     // one-hot columns in groups of CG: the group's indices in one round of independent loads, then its
@@ -309,7 +296,7 @@ __device__ __forceinline__ void logreg_eval_body(const LogregEvalArgs& a, int bx
   if ((tid & 63) == 0) red[tid >> 6] = lossv;
   __syncthreads();                                 // rs / red complete; the last chunk is in xs
   const int SW = Fd * KP + KP + 1;
-  float* slab = a.slab + ((int64_t)bt * gdx + bx) * SW;
+  float* slab = a.slab + ((int64_t)bt * gridDim.x + bx) * SW;
   HAR_LR_STAMP(4)
   // ---- pass B: dense gradient R^T X of the tile, chunks newest-first (fixed row order) ----
   for (int ch = nchunk - 1; ch >= 0; --ch) {
@@ -319,34 +306,23 @@ __device__ __forceinline__ void logreg_eval_body(const LogregEvalArgs& a, int bx
       eval_stage_chunk<KP, XLD>(a, W, wd, xs, c0, nc, r0, nrow_tile, false);
       __syncthreads();
     }
-    if constexpr (MF) {
-      // wave wv: rows 64 wv .. + 63 of R^T . X for every 16-column block of the chunk -> pb[wv]
-      for (int fb = 0; fb * 16 < nc; ++fb) {
-        f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+    // wave wv: rows 64 wv .. + 63 of R^T . X for every 16-column block of the chunk -> pb[wv]
+    for (int fb = 0; fb * 16 < nc; ++fb) {
+      f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 4
-        for (int i0 = 0; i0 < 64; i0 += 4) {
-          const int row = wv * 64 + i0 + kq;
-          const float av = l16 < KP ? rs[row * KP + l16] : 0.f;   // A = R^T [class l16][row]
-          acc = mfma4(av, xs[row * XLD + fb * 16 + l16], acc);     // B = X [row][column fb 16 + l16]
-        }
-        const int j = fb * 16 + l16;                               // D: column j, classes 4 kq + r
+      for (int i0 = 0; i0 < 64; i0 += 4) {
+        const int row = wv * 64 + i0 + kq;
+        const float av = l16 < KP ? rs[row * KP + l16] : 0.f;   // A = R^T [class l16][row]
+        acc = mfma4(av, xs[row * XLD + fb * 16 + l16], acc);     // B = X [row][column fb 16 + l16]
+      }
+      const int j = fb * 16 + l16;                               // D: column j, classes 4 kq + r
 #pragma unroll
-        for (int r = 0; r < 4; ++r)
-          if (j < nc && 4 * kq + r < KP) pb[(wv * EVAL_DCH + j) * KP + 4 * kq + r] = acc[r];
-      }
-      __syncthreads();
-      for (int o = tid; o < nc * KP; o += EVAL_ROWS)
-        slab[(int64_t)c0 * KP + o] = (pb[o] + pb[EVAL_DCH * KP + o]) + (pb[2 * EVAL_DCH * KP + o] + pb[3 * EVAL_DCH * KP + o]);
-    } else {
-      // (one 256-row chain per output: four interleaved chains and row ranges on more threads both
-      // measured slower, the reads being the bound — r5 stamps)
-      for (int o = tid; o < nc * KP; o += EVAL_ROWS) {
-        const int j = o / KP, k = o % KP;
-        float acc = 0.f;
-        for (int i = 0; i < EVAL_ROWS; ++i) acc = fmaf(rs[i * KP + k], xs[i * xld + j], acc);
-        slab[(int64_t)c0 * KP + o] = acc;
-      }
+      for (int r = 0; r < 4; ++r)
+        if (j < nc && 4 * kq + r < KP) pb[(wv * EVAL_DCH + j) * KP + 4 * kq + r] = acc[r];
     }
+    __syncthreads();
+    for (int o = tid; o < nc * KP; o += EVAL_ROWS)
+      slab[(int64_t)c0 * KP + o] = (pb[o] + pb[EVAL_DCH * KP + o]) + (pb[2 * EVAL_DCH * KP + o] + pb[3 * EVAL_DCH * KP + o]);
   }
   HAR_LR_STAMP(5)
   // intercept gradient sum R of the tile
@@ -371,21 +347,18 @@ __device__ __forceinline__ void logreg_eval_body(const LogregEvalArgs& a, int bx
   HAR_LR_STAMP(6)
 }
 
-template <int KP, int XLD, bool STAMP = false>
-__global__ __launch_bounds__(EVAL_ROWS) void logreg_eval_kernel(LogregEvalArgs a, uint64_t* st) {
-  extern __shared__ float smem[];
-  logreg_eval_body<KP, XLD, STAMP>(a, blockIdx.x, blockIdx.y, gridDim.x, smem, st);
-}
-
 // ---------------------------------------------------------------------------------------------
-// logreg_grad: G[bt][k][col], loss[bt].  Workgroup w owns the columns [256 w, 256 w + 256) and the
-// row SLICES of its one-hot columns: a column's CSC row list is cut into slices of a.SL rows
-// (col_slice = exclusive scan of ceil(rows / SL), built on the device by logreg_col_slices), so a
-// frequent category — '?' in XPEAK, hundreds of rows — is spread over many lanes instead of
-// serializing one.  The workgroup walks its slices in rounds of 256: one lane per slice sums its
-// rows' residuals into LDS, then one lane per column adds its slices of the round in order (or
-// the tile slabs of a dense column / the intercept).  Fixed summation order everywhere: bitwise
-// reproducible, and no host-side partition (the grid is ceil((F+1) / 256) x models).
+// logreg_grad: G[bt][k][col], loss[bt], one workgroup per (column block, trial model).  A one-hot
+// column's CSC row list is cut into slices of a.SL rows (col_slice = exclusive scan of
+// ceil(rows / SL), built on the device by logreg_col_slices), so a frequent category — '?' in XPEAK,
+// hundreds of rows — is spread over many lanes instead of serializing one.  The column blocks are
+// balanced (col_blk, ops/logreg.py LogregDesign.col_blocks): block bx = the columns [c0, c1), at most
+// 256, and their slices [s0, s1), at most 256 unless a lone column has more; slice sl covers the CSC
+// rows [srow[sl], srow[sl + 1]).  Everything a lane needs is loaded in ONE round at entry (its
+// slice's rows, its column's slice range, inv_std and pmask).  The workgroup walks its slices in
+// rounds of 256: one lane per slice sums its rows' residuals into LDS, then one lane per column adds
+// its slices of the round in order (or the tile slabs of a dense column / the intercept).  Fixed
+// summation order everywhere: bitwise reproducible.
 // ---------------------------------------------------------------------------------------------
 // Exact loss transport for the data-parallel bucket: a rank's fp64 loss as a 2^-40 fixed-point
 // int64 in four 16-bit pieces (three unsigned, the top one signed) carried as fp32 integers, plus
@@ -418,41 +391,22 @@ __device__ __forceinline__ double loss_decode(const float* in) {
   return (double)q / LOSS_FX;
 }
 
-// TB trial models per workgroup (TB = 4, opt-in: the four trials of one spec, launches with tstride 1):
-// the slice row lists, the column metadata and inv_std / pmask loaded once for the TB models and their
-// residual rows gathered together.  The sums per model and their order are those of TB = 1.
-template <int KP, bool STAMP = false, int TB = 1>
-__device__ __forceinline__ void logreg_grad_body(const LogregGradArgs& a, int bx, int by, uint64_t* st = nullptr) {
+template <int KP, bool STAMP = false>
+__global__ __launch_bounds__(256) void logreg_grad_kernel(LogregGradArgs a, uint64_t* st) {
   HAR_LR_STAMP(0)
-  __shared__ float part[256 * KP * TB];
-  __shared__ int cs_l[257];                        // col_slice[c0 .. c1] of the block
+  __shared__ float part[256 * KP];
   __shared__ float tl[256];                        // tile losses (block 0)
-  const int bt0 = a.model0 + TB * by * a.tstride;  // model of trial slot 0 (slot tt: bt0 + tt * tstride)
-  const int s = bt0 / a.T;                         // (TB > 1: the TB models share the spec)
+  const int bx = blockIdx.x, by = blockIdx.y;      // (column block, trial slot of the launch)
+  const int bt = a.model0 + by * a.tstride;        // trial model
+  const int s = bt / a.T;
   const int Fp1 = a.F + 1;
   const int SW = a.Fd * KP + KP + 1;
-  // col_blk (balanced blocks, ops/logreg.py LogregDesign.col_blocks): block bx = columns [c0, c1), slices
-  // [s0, s1), and slice sl covers the CSC rows [srow[sl], srow[sl + 1]) — no slice -> column search;
-  // everything a lane needs is loaded in ONE round at entry (its slice's rows, its column's slice range,
-  // inv_std and pmask).  Without it: fixed 256-column blocks, the slice's column searched in LDS
-  const bool fast = a.col_blk != nullptr;
-  int c0, c1, s0 = 0, s1 = 0;
-  if (fast) {
-    const int4 bk = reinterpret_cast<const int4*>(a.col_blk)[bx];
-    c0 = bk.x; c1 = bk.y; s0 = bk.z; s1 = bk.w;
-  } else {
-    c0 = bx * 256;
-    c1 = min(Fp1, c0 + 256);
-  }
+  const int4 bk = reinterpret_cast<const int4*>(a.col_blk)[bx];
+  const int c0 = bk.x, c1 = bk.y, s0 = bk.z, s1 = bk.w;
   const int col = c0 + threadIdx.x;
   int cs0 = 0, cs1 = 0, r0f = 0, r1f = 0;
-  if (fast) {
-    if (col < c1) { cs0 = a.col_slice[col]; cs1 = a.col_slice[col + 1]; }
-    if (s0 + (int)threadIdx.x < s1) { r0f = a.srow[s0 + threadIdx.x]; r1f = a.srow[s0 + threadIdx.x + 1]; }
-  } else {
-    if (c0 + (int)threadIdx.x <= c1) cs_l[threadIdx.x] = a.col_slice[c0 + threadIdx.x];
-    if (threadIdx.x == 0 && c1 - c0 == 256) cs_l[256] = a.col_slice[c1];
-  }
+  if (col < c1) { cs0 = a.col_slice[col]; cs1 = a.col_slice[col + 1]; }
+  if (s0 + (int)threadIdx.x < s1) { r0f = a.srow[s0 + threadIdx.x]; r1f = a.srow[s0 + threadIdx.x + 1]; }
   // the output scaling of this lane's column, loaded now (its latency hides behind the sums)
   const int64_t D = (int64_t)a.K * Fp1;
   float sc = 1.f, pmv[KP];
@@ -466,102 +420,67 @@ __device__ __forceinline__ void logreg_grad_body(const LogregGradArgs& a, int bx
       if (k < a.K) pmv[k] = pm[(int64_t)k * Fp1 + col];
   }
   const bool loss_block = bx == 0;
-#pragma unroll
-  for (int tt = 0; tt < TB; ++tt) {
-    const int bt = bt0 + tt * a.tstride;
-    const float* slab = a.slab + (int64_t)bt * a.ntiles * SW;
-    if (tt) __syncthreads();  // tl consumed
-    if (loss_block && (int)threadIdx.x < a.ntiles) tl[threadIdx.x] = slab[(int64_t)threadIdx.x * SW + SW - 1];
-    __syncthreads();
-    if (loss_block && threadIdx.x == 0) {
-      double l = 0.0;
-      for (int t = 0; t < a.ntiles; ++t)  // tile order (ntiles > 256: the rest straight from the slabs)
-        l += (double)(t < 256 ? tl[t] : slab[(int64_t)t * SW + SW - 1]);
-      if (a.loss_fx)
-        loss_encode(l, a.loss_fx + (int64_t)bt * 5);
-      else
-        a.loss[bt] = l;
-    }
+  const float* slab = a.slab + (int64_t)bt * a.ntiles * SW;
+  if (loss_block && (int)threadIdx.x < a.ntiles) tl[threadIdx.x] = slab[(int64_t)threadIdx.x * SW + SW - 1];
+  __syncthreads();
+  if (loss_block && threadIdx.x == 0) {
+    double l = 0.0;
+    for (int t = 0; t < a.ntiles; ++t)  // tile order (ntiles > 256: the rest straight from the slabs)
+      l += (double)(t < 256 ? tl[t] : slab[(int64_t)t * SW + SW - 1]);
+    if (a.loss_fx)
+      loss_encode(l, a.loss_fx + (int64_t)bt * 5);
+    else
+      a.loss[bt] = l;
   }
   HAR_LR_STAMP(1)
-  if (!fast) {
-    s0 = cs_l[0];
-    s1 = cs_l[c1 - c0];
-    cs0 = col < c1 ? cs_l[threadIdx.x] : 0;
-    cs1 = col < c1 ? cs_l[threadIdx.x + 1] : 0;
-  }
-  const float* R = a.R + (int64_t)TB * by * a.N * KP;  // this launch's residual slots of the TB models
-  float g[TB][KP];
+  const float* R = a.R + (int64_t)by * a.N * KP;  // this launch's residual slot of the model
+  float g[KP];
 #pragma unroll
-  for (int tt = 0; tt < TB; ++tt)
-#pragma unroll
-    for (int k = 0; k < KP; ++k) g[tt][k] = 0.f;
+  for (int k = 0; k < KP; ++k) g[k] = 0.f;
   for (int base = s0; base < s1; base += 256) {
     if (base > s0) __syncthreads();  // the previous round's partials are consumed
     const int sl = base + threadIdx.x;
     if (sl < s1) {
-      int r0, r1;
-      if (fast) {
-        r0 = base == s0 ? r0f : a.srow[sl];
-        r1 = base == s0 ? r1f : a.srow[sl + 1];
-      } else {
-        // the slice's column: the last column of the block whose first slice is <= sl
-        int lo = 0, hi = c1 - c0 - 1;
-        while (lo < hi) {
-          const int mid = (lo + hi + 1) >> 1;
-          if (cs_l[mid] <= sl) lo = mid; else hi = mid - 1;
-        }
-        r0 = a.csc_off[c0 + lo] + (sl - cs_l[lo]) * a.SL;
-        r1 = min(r0 + a.SL, a.csc_off[c0 + lo + 1]);
-      }
-      float gs[TB][KP];
+      const int r0 = base == s0 ? r0f : a.srow[sl];
+      const int r1 = base == s0 ? r1f : a.srow[sl + 1];
+      float gs[KP];
 #pragma unroll
-      for (int tt = 0; tt < TB; ++tt)
-#pragma unroll
-        for (int k = 0; k < KP; ++k) gs[tt][k] = 0.f;
-      // groups of RG rows: RG row indices, then their RG residual rows (of each of the TB models) in
-      // flight (two dependent round trips per group, the slice's last partial group included: rows past
-      // r1 re-read row r1 - 1 and add +0, an exact identity since gs is never -0 — the sums are bitwise
-      // the row-by-row ones; a row-at-a-time tail cost two round trips PER ROW: grad stamps)
-      constexpr int RG = TB > 1 ? 4 : (KP == 8 ? 8 : 4);
+      for (int k = 0; k < KP; ++k) gs[k] = 0.f;
+      // groups of RG rows: RG row indices, then their RG residual rows in flight (two dependent round
+      // trips per group, the slice's last partial group included: rows past r1 re-read row r1 - 1 and
+      // add +0, an exact identity since gs is never -0 — the sums are bitwise the row-by-row ones; a
+      // row-at-a-time tail cost two round trips PER ROW: grad stamps)
+      constexpr int RG = KP == 8 ? 8 : 4;
       for (int i0 = r0; i0 < r1; i0 += RG) {
         int rid[RG];
 #pragma unroll
         for (int j = 0; j < RG; ++j) rid[j] = a.csc_rows[min(i0 + j, r1 - 1)];
-        f32x4_t rr[TB][RG][KP / 4];
+        f32x4_t rr[RG][KP / 4];
 #pragma unroll
-        for (int tt = 0; tt < TB; ++tt)
+        for (int j = 0; j < RG; ++j)
 #pragma unroll
-          for (int j = 0; j < RG; ++j)
-#pragma unroll
-            for (int q = 0; q < KP / 4; ++q)
-              rr[tt][j][q] = reinterpret_cast<const f32x4_t*>(R + ((int64_t)tt * a.N + rid[j]) * KP)[q];
+          for (int q = 0; q < KP / 4; ++q)
+            rr[j][q] = reinterpret_cast<const f32x4_t*>(R + (int64_t)rid[j] * KP)[q];
 #pragma unroll
         for (int j = 0; j < RG; ++j) {
           const bool on = i0 + j < r1;
 #pragma unroll
-          for (int tt = 0; tt < TB; ++tt)
-#pragma unroll
-            for (int q = 0; q < KP / 4; ++q) {
-              gs[tt][4 * q + 0] += on ? rr[tt][j][q][0] : 0.f;
-              gs[tt][4 * q + 1] += on ? rr[tt][j][q][1] : 0.f;
-              gs[tt][4 * q + 2] += on ? rr[tt][j][q][2] : 0.f;
-              gs[tt][4 * q + 3] += on ? rr[tt][j][q][3] : 0.f;
-            }
+          for (int q = 0; q < KP / 4; ++q) {
+            gs[4 * q + 0] += on ? rr[j][q][0] : 0.f;
+            gs[4 * q + 1] += on ? rr[j][q][1] : 0.f;
+            gs[4 * q + 2] += on ? rr[j][q][2] : 0.f;
+            gs[4 * q + 3] += on ? rr[j][q][3] : 0.f;
+          }
         }
       }
 #pragma unroll
-      for (int tt = 0; tt < TB; ++tt)
-#pragma unroll
-        for (int k = 0; k < KP; ++k) part[(threadIdx.x * TB + tt) * KP + k] = gs[tt][k];
+      for (int k = 0; k < KP; ++k) part[threadIdx.x * KP + k] = gs[k];
     }
     __syncthreads();
     const int e0 = max(cs0, base), e1 = min(cs1, base + 256);
     for (int e = e0; e < e1; ++e) {  // this column's slices of the round, in order
 #pragma unroll
-      for (int tt = 0; tt < TB; ++tt)
-#pragma unroll
-        for (int k = 0; k < KP; ++k) g[tt][k] += part[((e - base) * TB + tt) * KP + k];
+      for (int k = 0; k < KP; ++k) g[k] += part[(e - base) * KP + k];
     }
   }
   HAR_LR_STAMP(2)
@@ -569,39 +488,19 @@ __device__ __forceinline__ void logreg_grad_body(const LogregGradArgs& a, int bx
   const int cm = a.col_map[col];
   if (cm >= 0 || cm == -1) {  // dense column j = cm, or the intercept (slab entries after the dense block)
     const int off = cm >= 0 ? cm * KP : a.Fd * KP;
-#pragma unroll
-    for (int tt = 0; tt < TB; ++tt) {
-      const float* slab = a.slab + (int64_t)(bt0 + tt * a.tstride) * a.ntiles * SW;
 #pragma unroll 8
-      for (int t = 0; t < a.ntiles; ++t) {
-        const float* p = slab + (int64_t)t * SW + off;
+    for (int t = 0; t < a.ntiles; ++t) {
+      const float* p = slab + (int64_t)t * SW + off;
 #pragma unroll
-        for (int k = 0; k < KP; ++k) g[tt][k] += p[k];
-      }
+      for (int k = 0; k < KP; ++k) g[k] += p[k];
     }
   }
   HAR_LR_STAMP(3)
+  float* G = a.G + (int64_t)bt * D;
 #pragma unroll
-  for (int tt = 0; tt < TB; ++tt) {
-    float* G = a.G + (int64_t)(bt0 + tt * a.tstride) * D;
-#pragma unroll
-    for (int k = 0; k < KP; ++k)
-      if (k < a.K) G[(int64_t)k * Fp1 + col] = g[tt][k] * sc * pmv[k];
-  }
+  for (int k = 0; k < KP; ++k)
+    if (k < a.K) G[(int64_t)k * Fp1 + col] = g[k] * sc * pmv[k];
   HAR_LR_STAMP(4)
-}
-
-template <int KP, bool STAMP = false, int TB = 1>
-__global__ __launch_bounds__(256) void logreg_grad_kernel(LogregGradArgs a, uint64_t* st) {
-  logreg_grad_body<KP, STAMP, TB>(a, blockIdx.x, blockIdx.y, st);
-}
-// the same body held to 5+ waves per SIMD (94 VGPRs): more resident workgroups for the batched
-// CrossValidator launch — opt-in (HAR_LR_GRAD_WPE=5): LR-CV 4.07-4.24 vs 4.12-4.17 ms, within noise
-// (profiles/r5/lr_grad_blocks.md)
-template <int KP>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void logreg_grad_kernel_w5(LogregGradArgs a,
-                                                                                                  uint64_t* st) {
-  logreg_grad_body<KP, false, 1>(a, blockIdx.x, blockIdx.y, st);
 }
 
 // after the data-parallel all-reduce of the bucket: the summed fixed-point losses -> fp64
@@ -931,9 +830,11 @@ __device__ __forceinline__ DirElem dir_load(const QnArgs& a, int b, int k, int c
 
 // phase 1
 template <int KP, bool FULLM, bool STAMP = false>
-__device__ __forceinline__ void qn_direction_body(const QnArgs& a, int c, int b, uint64_t* st = nullptr,
-                                                  float* wt = nullptr) {
+__global__ __launch_bounds__(QN_BLOCK) void qn_direction_kernel(QnArgs a, uint64_t* st, int use_wt) {
+  extern __shared__ float wtile[];
   HAR_LR_STAMP(0)
+  const int c = blockIdx.x, b = blockIdx.y;  // (chunk, model)
+  float* wt = use_wt ? wtile : nullptr;
   __shared__ double sh[4 * NP2];
   __shared__ float cS[QN_MAX_M], cY[QN_MAX_M];
   __shared__ float gam;
@@ -1161,12 +1062,6 @@ __device__ __forceinline__ void qn_direction_body(const QnArgs& a, int c, int b,
   HAR_LR_STAMP(5)
 }
 
-template <int KP, bool FULLM, bool STAMP = false>
-__global__ __launch_bounds__(QN_BLOCK) void qn_direction_kernel(QnArgs a, uint64_t* st, int use_wt) {
-  extern __shared__ float wtile[];
-  qn_direction_body<KP, FULLM, STAMP>(a, blockIdx.x, blockIdx.y, st, use_wt ? wtile : nullptr);
-}
-
 // One parameter element's phase-2 operands that do not depend on the picked trial (x, g, L1 / L2
 // weights, the history values), loaded at a clamped (valid) index: the first three elements of every
 // thread go out at the start of the launch, under the P2 reduction and the pick, and a refill three
@@ -1201,8 +1096,9 @@ __device__ __forceinline__ UpdElem upd_load(const QnArgs& a, int b, int e) {
 
 // phase 2
 template <bool FULLM, bool WIDE, bool STAMP = false>
-__device__ __forceinline__ void qn_update_body(const QnArgs& a, int c, int b, uint64_t* st = nullptr) {
+__global__ __launch_bounds__(QN_BLOCK) void qn_update_kernel(QnArgs a, uint64_t* st) {
   HAR_LR_STAMP(0)
+  const int c = blockIdx.x, b = blockIdx.y;  // (chunk, model)
   __shared__ double sh[4 * (NP3 + 2 * QN_MAX_M)];
   __shared__ double p2v[NP2];
   __shared__ double fin_v[NP3], p1t[NP1];
@@ -1389,105 +1285,6 @@ __device__ __forceinline__ void qn_update_body(const QnArgs& a, int c, int b, ui
   HAR_LR_STAMP(7)
 }
 
-template <bool FULLM, bool WIDE, bool STAMP = false>
-__global__ __launch_bounds__(QN_BLOCK) void qn_update_kernel(QnArgs a, uint64_t* st) {
-  qn_update_body<FULLM, WIDE, STAMP>(a, blockIdx.x, blockIdx.y, st);
-}
-
-// ---------------------------------------------------------------------------------------------
-// Persistent solve: the whole fit's launch sequence (logreg_solve_run in bind.cpp: init direction,
-// evaluate, gradient, init update, then max_iter x [direction, evaluate, gradient, update]) as ONE
-// cooperative launch.  Every phase runs the SAME body as its stand-alone kernel over virtual blocks
-// (workgroup g takes blocks g, g + grid, ...), so the solve is bitwise the launch sequence's; a
-// grid barrier replaces each kernel boundary.  Barrier: an agent-scope release fence (this XCD's
-// L2 written back), one counter increment, a bounded spin on the counter, an agent-scope acquire
-// fence (stale L1 / L2 lines dropped).  The spin is bounded and a timed-out barrier raises a flag
-// that every later barrier checks first, so a fault can never leave waves spinning: the launcher
-// reports the flag and the caller falls back to the launch sequence.
-// ---------------------------------------------------------------------------------------------
-struct SolvePersistArgs {
-  QnArgs q;
-  LogregEvalArgs evT, ev1;  // the init evaluation (trial 0 of every model) / the per-iteration one
-  LogregGradArgs grT, gr1;
-  int nT, n1, max_iter;
-  uint32_t* sync;           // [0] barrier counter (zeroed by the launcher), [1] timeout flag
-  uint32_t spin_limit;      // polls per barrier before the timeout flag is raised
-};
-
-constexpr uint32_t SOLVE_SPIN_LIMIT = 1u << 22;
-// (tests shrink it to force the timeout path: har_logreg_set_spin_limit)
-uint32_t g_solve_spin_limit = SOLVE_SPIN_LIMIT;
-
-__device__ __forceinline__ void grid_barrier(uint32_t* sync, uint32_t& gen, uint32_t spin_limit) {
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    __hip_atomic_fetch_add(sync, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const uint32_t target = (gen + 1) * gridDim.x;
-    uint32_t spins = 0;
-    while (__hip_atomic_load(sync, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-      if (__hip_atomic_load(sync + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) break;
-      if (++spins > spin_limit) {
-        __hip_atomic_store(sync + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        break;
-      }
-      __builtin_amdgcn_s_sleep(2);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  }
-  ++gen;
-  __syncthreads();
-}
-
-template <int KP, int XLD, bool FULLM>
-__global__ __launch_bounds__(QN_BLOCK) void logreg_solve_persistent_kernel(SolvePersistArgs p) {
-  extern __shared__ float smem[];
-  uint32_t gen = 0;
-  const int G = gridDim.x, g0 = blockIdx.x;
-  const int nqb = p.q.nch * p.q.B;
-  const int tiles = (int)((p.ev1.N + EVAL_ROWS - 1) / EVAL_ROWS);
-  const int cols = p.gr1.col_blk ? p.gr1.nblk : (p.gr1.F + 1 + 255) / 256;  // (grT: the same design)
-  auto qn = [&](int phase, int head, int filled, int init, int fin_it) {
-    QnArgs a = p.q;
-    a.head = head;
-    a.filled = filled;
-    a.init = init;
-    a.fin_it = fin_it;
-    for (int v = g0; v < nqb; v += G) {
-      if (phase == 1)
-        qn_direction_body<KP, FULLM>(a, v % a.nch, v / a.nch);
-      else
-        qn_update_body<FULLM, FULLM>(a, v % a.nch, v / a.nch);
-      __syncthreads();  // the next virtual block reuses the LDS
-    }
-    grid_barrier(p.sync, gen, p.spin_limit);
-  };
-  auto evaluate = [&](const LogregEvalArgs& ev, const LogregGradArgs& gr, int n) {
-    for (int v = g0; v < tiles * n; v += G) {
-      logreg_eval_body<KP, XLD>(ev, v % tiles, v / tiles, tiles, smem);
-      __syncthreads();
-    }
-    grid_barrier(p.sync, gen, p.spin_limit);
-    for (int v = g0; v < cols * n; v += G) {
-      logreg_grad_body<KP>(gr, v % cols, v / cols);
-      __syncthreads();
-    }
-    grid_barrier(p.sync, gen, p.spin_limit);
-  };
-  qn(1, 0, 0, 1, 0);
-  evaluate(p.evT, p.grT, p.nT);
-  qn(2, 0, 0, 1, 0);
-  const int mm = p.q.m;
-  int head = 0, filled = 0;
-  for (int it = 0; it < p.max_iter; ++it) {
-    qn(1, head, filled, 0, 0);
-    evaluate(p.ev1, p.gr1, p.n1);
-    qn(2, head, filled, 0, it + 1);
-    head = (head + 1) % mm;
-    filled = filled + 1 < mm ? filled + 1 : mm;
-  }
-}
-
 }  // namespace
 
 extern "C" int har_logreg_eval(const LogregEvalArgs* args, int KP, int n_models, hipStream_t s) {
@@ -1497,42 +1294,21 @@ extern "C" int har_logreg_eval(const LogregEvalArgs* args, int KP, int n_models,
     return -2;
   if (a.N == 0 || n_models == 0) return 0;
   const int tiles = (int)((a.N + EVAL_ROWS - 1) / EVAL_ROWS);
-  static const bool mf_on = [] {
-    const char* e = std::getenv("HAR_LR_EVAL_MFMA");
-    return !e || std::atoi(e) != 0;
-  }();
-  static const int mfn_mode = [] {  // narrow designs on the MFMA kernel: 1 always, 0 never, -1 small launches
-    const char* e = std::getenv("HAR_LR_EVAL_MFN");
-    return e ? std::atoi(e) : 1;
-  }();
-  const bool narrow = eval_xld(a.Fd) == EVAL_XLD_NARROW;
-  const bool mf = mf_on && (!narrow || mfn_mode == 1 || (mfn_mode < 0 && (int64_t)tiles * n_models <= 256));
-  const int xld = mf ? (narrow ? EVAL_XLD_MFN : EVAL_XLD_MF) : eval_xld(a.Fd);
-  const size_t lds = sizeof(float) * (EVAL_DCH * KP + EVAL_ROWS * xld + EVAL_ROWS * KP + EVAL_ROWS / 64 +
-                                      (mf ? 4 * EVAL_DCH * KP : 0));
+  const bool narrow = a.Fd <= EVAL_NARROW_FD;
+  const size_t lds = sizeof(float) * (EVAL_DCH * KP + EVAL_ROWS * (narrow ? EVAL_XLD_MFN : EVAL_XLD_MF) +
+                                      EVAL_ROWS * KP + EVAL_ROWS / 64 + 4 * EVAL_DCH * KP);
   dim3 grid(tiles, n_models);
-  if (mf && narrow && KP == 8)
+  if (narrow && KP == 8)
     if (g_lr_stamps)
       logreg_eval_kernel<8, EVAL_XLD_MFN, true><<<grid, EVAL_ROWS, lds, s>>>(a, g_lr_stamps);
     else
       logreg_eval_kernel<8, EVAL_XLD_MFN><<<grid, EVAL_ROWS, lds, s>>>(a, nullptr);
-  else if (mf && narrow)
-    logreg_eval_kernel<16, EVAL_XLD_MFN><<<grid, EVAL_ROWS, lds, s>>>(a, nullptr);
-  else if (mf && KP == 8)
-    logreg_eval_kernel<8, EVAL_XLD_MF><<<grid, EVAL_ROWS, lds, s>>>(a, nullptr);
-  else if (mf)
-    logreg_eval_kernel<16, EVAL_XLD_MF><<<grid, EVAL_ROWS, lds, s>>>(a, nullptr);
-  else if (KP == 8 && narrow)
-    if (g_lr_stamps)
-      logreg_eval_kernel<8, EVAL_XLD_NARROW, true><<<grid, EVAL_ROWS, lds, s>>>(a, g_lr_stamps);
-    else
-      logreg_eval_kernel<8, EVAL_XLD_NARROW><<<grid, EVAL_ROWS, lds, s>>>(a, nullptr);
-  else if (KP == 8)
-    logreg_eval_kernel<8, EVAL_DCH + 1><<<grid, EVAL_ROWS, lds, s>>>(a, nullptr);
   else if (narrow)
-    logreg_eval_kernel<16, EVAL_XLD_NARROW><<<grid, EVAL_ROWS, lds, s>>>(a, nullptr);
+    logreg_eval_kernel<16, EVAL_XLD_MFN><<<grid, EVAL_ROWS, lds, s>>>(a, nullptr);
+  else if (KP == 8)
+    logreg_eval_kernel<8, EVAL_XLD_MF><<<grid, EVAL_ROWS, lds, s>>>(a, nullptr);
   else
-    logreg_eval_kernel<16, EVAL_DCH + 1><<<grid, EVAL_ROWS, lds, s>>>(a, nullptr);
+    logreg_eval_kernel<16, EVAL_XLD_MF><<<grid, EVAL_ROWS, lds, s>>>(a, nullptr);
   HAR_CHECK_LAUNCH();
   return 0;
 }
@@ -1542,36 +1318,11 @@ extern "C" int har_logreg_eval_tiles(int64_t n) { return (int)((n + EVAL_ROWS - 
 extern "C" int har_logreg_grad(const LogregGradArgs* args, int KP, int n_models, hipStream_t s) {
   const LogregGradArgs& a = *args;
   if (a.K < 1 || a.K > KP || (KP != 8 && KP != 16) || a.T < 1 || a.tstride < 1 || a.SL < 1 ||
-      a.col_slice == nullptr || a.csc_off == nullptr || (a.loss == nullptr && a.loss_fx == nullptr))
+      a.col_slice == nullptr || a.csc_off == nullptr || (a.loss == nullptr && a.loss_fx == nullptr) ||
+      a.col_blk == nullptr || a.nblk < 1 || a.srow == nullptr)
     return -2;
   if (n_models == 0) return 0;
-  if (a.col_blk && (a.nblk < 1 || a.srow == nullptr)) return -2;
-  // opt-in (HAR_LR_GRAD_TB=4): four trial models per workgroup for large launches of consecutive trials
-  // of one spec — measured SLOWER for the batched CrossValidator (grad 54.8 vs 35.6 us per launch, LR-CV
-  // 4.8-5.3 vs 4.1-4.5 ms: a quarter of the workgroups, each with 4x the gathers in flight per lane,
-  // profiles/r5/lr_grad_blocks.md)
-  static const int tb_env = [] {
-    const char* e = std::getenv("HAR_LR_GRAD_TB");
-    return e ? std::atoi(e) : 1;
-  }();
-  const bool tb4 = tb_env == 4 && KP == 8 && a.T == 4 && a.tstride == 1 && a.model0 % 4 == 0 && n_models % 4 == 0 &&
-                   n_models >= 64;
-  if (tb4) {
-    dim3 g4(a.col_blk ? a.nblk : (a.F + 1 + 255) / 256, n_models / 4);
-    logreg_grad_kernel<8, false, 4><<<g4, 256, 0, s>>>(a, nullptr);
-    HAR_CHECK_LAUNCH();
-    return 0;
-  }
-  dim3 grid(a.col_blk ? a.nblk : (a.F + 1 + 255) / 256, n_models);
-  static const int wpe_env = [] {
-    const char* e = std::getenv("HAR_LR_GRAD_WPE");
-    return e ? std::atoi(e) : 0;
-  }();
-  if (KP == 8 && wpe_env == 5 && (int64_t)grid.x * grid.y >= 1024 && !g_lr_stamps_grd) {
-    logreg_grad_kernel_w5<8><<<grid, 256, 0, s>>>(a, nullptr);
-    HAR_CHECK_LAUNCH();
-    return 0;
-  }
+  dim3 grid(a.nblk, n_models);
   if (KP == 8)
     if (g_lr_stamps_grd)
       logreg_grad_kernel<8, true><<<grid, 256, 0, s>>>(a, g_lr_stamps_grd);
@@ -1610,82 +1361,6 @@ extern "C" int har_qn_chunks(int64_t D, int B) {
   }();
   const int64_t by_b = budget / std::max(B, 1), by_d = (D + 255) / 256;
   return (int)std::max<int64_t>(1, std::min<int64_t>(QN_MAX_CHUNKS, std::min(by_b, by_d)));
-}
-
-// Host-side validation of one evaluation's arguments (the checks of har_logreg_eval / har_logreg_grad).
-static bool eval_args_ok(const LogregEvalArgs& a, const LogregGradArgs& g, int KP, int n) {
-  return a.Fd >= 0 && a.K >= 1 && a.K <= KP && a.T >= 1 && a.tstride >= 1 && a.slab != nullptr &&
-         (a.C == 0 || a.cat != nullptr) && a.mode == 0 && g.K == a.K && g.T == a.T && g.SL >= 1 &&
-         g.col_slice != nullptr && g.csc_off != nullptr && g.loss != nullptr && g.loss_fx == nullptr &&
-         g.N == a.N && g.F == a.F && g.Fd == a.Fd && g.tstride == a.tstride && g.model0 == a.model0 &&
-         g.ntiles == (int)((a.N + EVAL_ROWS - 1) / EVAL_ROWS) && (g.col_blk == nullptr || (g.nblk >= 1 && g.srow != nullptr)) && n >= 1 && a.N > 0 && (a.C == 0 || a.R != nullptr);
-}
-
-// The whole solve as one cooperative launch (logreg_solve_persistent_kernel).  Returns 0 when it ran
-// (the caller then checks the timeout flag sync[1] with its results), -4 when this configuration
-// has no persistent instantiation (m != QN_MAX_M) or the grid cannot be co-resident (the caller uses
-// the launch sequence), -2 on invalid arguments.
-extern "C" int har_logreg_solve_persistent(const QnArgs* q, const LogregEvalArgs* evT, const LogregGradArgs* grT,
-                                           int nT, const LogregEvalArgs* ev1, const LogregGradArgs* gr1, int n1,
-                                           int KP, int max_iter, uint32_t* sync, int max_grid, hipStream_t s) {
-  const QnArgs& a = *q;
-  if ((KP != 8 && KP != 16) || a.K > KP || a.m < 1 || a.m > QN_MAX_M || a.T < 1 || a.T > QN_MAX_TRIALS ||
-      a.D != (int64_t)a.K * (a.F + 1) || a.D >= (1LL << 31) || a.nch != har_qn_chunks(a.D, a.B) || a.B < 1 ||
-      a.done == nullptr || sync == nullptr || max_iter < 0 || !eval_args_ok(*evT, *grT, KP, nT) ||
-      !eval_args_ok(*ev1, *gr1, KP, n1) || grT->col_blk != gr1->col_blk || grT->nblk != gr1->nblk || evT->N != ev1->N || evT->Fd != ev1->Fd || ev1->F != a.F ||
-      ev1->K != a.K || n1 != a.B * a.T || nT != a.B || ev1->tstride != 1 || evT->tstride != a.T)
-    return -2;
-  if (a.m != QN_MAX_M) return -4;
-  SolvePersistArgs p{*q, *evT, *ev1, *grT, *gr1, nT, n1, max_iter, sync, g_solve_spin_limit};
-  p.q.head = p.q.filled = p.q.init = p.q.fin_it = 0;
-  static const bool mf_on = [] {
-    const char* e = std::getenv("HAR_LR_EVAL_MFMA");
-    return !e || std::atoi(e) != 0;
-  }();
-  static const int mfn_mode = [] {
-    const char* e = std::getenv("HAR_LR_EVAL_MFN");
-    return e ? std::atoi(e) : 1;
-  }();
-  const bool narrow = eval_xld(ev1->Fd) == EVAL_XLD_NARROW;
-  const bool mf = mf_on && (!narrow || mfn_mode == 1);
-  const int xld = mf ? (narrow ? EVAL_XLD_MFN : EVAL_XLD_MF) : eval_xld(ev1->Fd);
-  const size_t lds = sizeof(float) * (EVAL_DCH * KP + EVAL_ROWS * xld + EVAL_ROWS * KP + EVAL_ROWS / 64 +
-                                      (mf ? 4 * EVAL_DCH * KP : 0));
-  const void* fn;
-  if (KP == 8)
-    fn = mf && narrow ? (const void*)logreg_solve_persistent_kernel<8, EVAL_XLD_MFN, true>
-       : mf ? (const void*)logreg_solve_persistent_kernel<8, EVAL_XLD_MF, true>
-            : narrow ? (const void*)logreg_solve_persistent_kernel<8, EVAL_XLD_NARROW, true>
-                     : (const void*)logreg_solve_persistent_kernel<8, EVAL_DCH + 1, true>;
-  else
-    fn = mf && narrow ? (const void*)logreg_solve_persistent_kernel<16, EVAL_XLD_MFN, true>
-       : mf ? (const void*)logreg_solve_persistent_kernel<16, EVAL_XLD_MF, true>
-            : narrow ? (const void*)logreg_solve_persistent_kernel<16, EVAL_XLD_NARROW, true>
-                     : (const void*)logreg_solve_persistent_kernel<16, EVAL_DCH + 1, true>;
-  // grid: every phase's virtual blocks once if they fit co-resident, else as many as are
-  int dev = 0, cus = 0, per_cu = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, QN_BLOCK, lds) != hipSuccess || per_cu < 1)
-    return -4;
-  const int tiles = (int)((ev1->N + EVAL_ROWS - 1) / EVAL_ROWS), cols = gr1->col_blk ? gr1->nblk : (a.F + 1 + 255) / 256;
-  const int64_t want = std::max<int64_t>({(int64_t)a.nch * a.B, (int64_t)tiles * n1, (int64_t)cols * n1});
-  if (max_grid < 0 && want > (int64_t)per_cu * cus) return -4;  // one co-resident round required
-  int64_t grid = std::min<int64_t>(want, (int64_t)per_cu * cus);
-  if (max_grid > 0) grid = std::min<int64_t>(grid, max_grid);
-  if (grid < 1) return -4;
-  if (hipMemsetAsync(sync, 0, 2 * sizeof(uint32_t), s) != hipSuccess) return -4;
-  void* kargs[] = {&p};
-  if (hipLaunchCooperativeKernel(fn, dim3((unsigned)grid), dim3(QN_BLOCK), kargs, (unsigned)lds, s) != hipSuccess) {
-    (void)hipGetLastError();
-    return -4;
-  }
-  return 0;
-}
-
-extern "C" uint32_t har_logreg_set_spin_limit(uint32_t n) {
-  const uint32_t old = g_solve_spin_limit;
-  g_solve_spin_limit = n ? n : SOLVE_SPIN_LIMIT;
-  return old;
 }
 
 extern "C" int har_lbfgs_phase(const QnArgs* args, int KP, int phase, hipStream_t s) {

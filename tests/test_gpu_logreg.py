@@ -290,83 +290,22 @@ def test_crossvalidator_batched_refit_matches_plain_fit_gpu(cuda):
     assert agree > 0.99, agree
 
 
-@pytest.mark.parametrize("specs_kind", ["pair", "wisdm"])
-def test_persistent_solve_equals_launch_sequence(cuda, wisdm_csv, specs_kind):
-    """The whole solve as ONE cooperative launch (logreg_solve_persistent_kernel: the same phase
-    bodies over virtual blocks, grid barriers for the kernel boundaries) is bitwise the launch
-    sequence: coefficients, intercepts and objective histories."""
-    from har.models.logreg import FitSpec, LogisticRegression
+def test_grad_rejects_a_null_col_blk(cuda):
+    """The gradient kernel has one path, over the balanced column blocks: its launcher rejects a null
+    ``col_blk`` on the host (no kernel is launched) as a contract violation."""
     from har.ops import _native
-    from har.ops import logreg as L
+    from har.ops.logreg import DeviceLogregSolver, LogregDesign
 
-    mod = _native.kernels()
-    if specs_kind == "pair":
-        _, y, hm = _hybrid_problem(cuda, N=3000, seed=9)
-        est = LogisticRegression(maxIter=20, regParam=0.1)
-        specs, K = [FitSpec(None, 0.1, 0.0), FitSpec(None, 0.3, 0.1)], 6
-        y = y.to(cuda)
-    else:
-        from har.features.hybrid import hybrid_features
-        from har.suite import load_wisdm
-        from har.models.base import labels_tensor, num_label_classes
-
-        train, _, _ = load_wisdm(wisdm_csv, "reference", 2018, device=cuda)
-        hm = hybrid_features(train, "features", cuda)
-        y = labels_tensor(train, "label", cuda)
-        K = num_label_classes(train, "label", cuda)
-        est = LogisticRegression(maxIter=20, regParam=0.3, elasticNetParam=0.8)
-        specs = [FitSpec(None, 0.3, 0.8)]
-    out, modes = [], []
-    old = mod.logreg_set_persistent(1)
-    try:
-        for mode in (1, 0):
-            mod.logreg_set_persistent(mode)
-            out.append(est.fit_many(hm, y, specs, K))
-            modes.append(L.LAST_SOLVE_MODE)
-    finally:
-        mod.logreg_set_persistent(old)
-    assert modes == [1, 0]
-    for m1, m2 in zip(*out):
-        assert torch.equal(m1.coefficientMatrix, m2.coefficientMatrix)
-        assert torch.equal(m1.interceptVector, m2.interceptVector)
-        assert m1.summary["objectiveHistory"] == m2.summary["objectiveHistory"]
-
-
-def test_persistent_solve_timeout_falls_back_to_the_sequence(cuda):
-    """A grid barrier of the persistent solve that runs out of polls raises the timeout flag; the
-    fit must not return the unsynchronized results: it is rerun as the launch sequence (mode 3) and
-    equals a plain launch-sequence fit bit for bit (the flag was never read)."""
-    import warnings
-
-    from har.models.logreg import FitSpec, LogisticRegression
-    from har.ops import _native
-    from har.ops import logreg as L
-
-    mod = _native.kernels()
-    _, y, hm = _hybrid_problem(cuda, N=3000, seed=9)
-    est = LogisticRegression(maxIter=20, regParam=0.1)
-    specs, K = [FitSpec(None, 0.1, 0.0), FitSpec(None, 0.3, 0.1)], 6
-    y = y.to(cuda)
-    old, old_lim = mod.logreg_set_persistent(2), mod.logreg_set_spin_limit(1)
-    try:
-        L.solver_cache_clear()
-        with warnings.catch_warnings(record=True) as w:
-            warnings.simplefilter("always")
-            a = est.fit_many(hm, y, specs, K)
-        mode_a = L.LAST_SOLVE_MODE
-        mod.logreg_set_persistent(0)
-        L.solver_cache_clear()
-        b = est.fit_many(hm, y, specs, K)
-    finally:
-        mod.logreg_set_persistent(old)
-        mod.logreg_set_spin_limit(old_lim)
-        L.solver_cache_clear()
-    if mode_a == -1 or mode_a == 0:
-        pytest.skip("the persistent solve was not co-resident on this device")
-    assert mode_a == 3 and any("timed out" in str(x.message) for x in w), mode_a
-    for m1, m2 in zip(a, b):
-        assert torch.equal(m1.coefficientMatrix, m2.coefficientMatrix)
-        assert torch.equal(m1.interceptVector, m2.interceptVector)
+    X, y, hm = _hybrid_problem(cuda, N=300, seed=11, blocks=((0, 12),), Fd=3, K=3)
+    F, K = X.shape[1], 3
+    design = LogregDesign(hm, y.to(cuda), None, K)
+    solver = DeviceLogregSolver(design, 1, 1, 4, torch.ones(1, F, device=cuda), torch.ones(1, K, F + 1, device=cuda),
+                                torch.full((1,), 1.0 / 300, device=cuda), torch.zeros(1, K * (F + 1), device=cuda),
+                                None, 1, 1e-6)
+    (_, gr), = solver._eval_args(1)
+    assert gr[22] == design.col_blocks()[0].data_ptr() != 0
+    with pytest.raises(RuntimeError, match="contract violation"):
+        _native.kernels().logreg_grad(gr[:22] + (0,) + gr[23:], _native.stream_ptr())
 
 
 def test_solver_cache_refit_is_bitwise_a_fresh_fit(cuda, wisdm_csv):

@@ -370,14 +370,6 @@ def test_solver_with_short_history(cuda, monkeypatch, alpha):
     xa, fa, ha, design = solve("1")
     xb, fb, hb, _ = solve("0")
     assert torch.equal(xa, xb) and torch.equal(fa, fb) and torch.equal(ha, hb)
-    old = mod.logreg_set_persistent(1)
-    try:
-        xc, fc, hc, _ = solve("1")
-        mode = LG.LAST_SOLVE_MODE
-    finally:
-        mod.logreg_set_persistent(old)
-    assert mode == 0, mode  # no persistent instantiation for m != 10: the launch sequence ran
-    assert torch.equal(xa, xc) and torch.equal(fa, fc) and torch.equal(ha, hc)
 
     ref_design = LG.LogregDesign(hm, y.to(cuda), rw.double(), K)
 

@@ -1,6 +1,6 @@
 #!/bin/bash
 # LR env A/B on one box: the device-LR GPU tests once, then the reference suite bench and the grad
-# kernel's phase stamps under each env assignment of VARS (';'-separated, e.g. "HAR_LR_COLBLK=0;HAR_LR_COLBLK=1").
+# kernel's phase stamps under each env assignment of VARS (';'-separated, e.g. "HAR_LR_WTILE=0;HAR_LR_WTILE=1").
 #   usage: VARS="A=1;A=0" gpurun --timeout 900 -- bash tools/gpu_lr_envab.sh <tag>
 set -u
 ROOT="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
