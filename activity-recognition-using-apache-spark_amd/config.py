@@ -79,6 +79,11 @@ class RunConfig:
     kmeans: int = 0
     kmeans_max_iter: int = 20
     kmeans_init: str = "k-means++"           # k-means++ | random
+    # GaussianMixture (new, opt-in): --gmm K fits a K-component mixture on the same dense numeric features
+    gmm: int = 0
+    gmm_max_iter: int = 100
+    gmm_cov: str = "full"                    # full | diag
+    gmm_init: str = "k-means"                # k-means | random
     # artefacts
     plots: bool = False
     report: bool = False                   # Results table + charts + index.html (report/summary.py)

@@ -48,6 +48,16 @@ class KMeansSummary:
                 "k": self.k}
 
 
+def cluster_label_map(k: int, device, pred: torch.Tensor, y: torch.Tensor, num_classes: int):
+    """The cluster x label table, the majority label per cluster and the purity (``KMeansModel.label_map``;
+    shared with ``GaussianMixtureModel``)."""
+    n = max(int(k), int(num_classes))
+    cm = OM.confusion_matrix(pred.to(device), y.to(device), n)[:int(k), :int(num_classes)]
+    total = cm.sum()
+    purity = float(cm.max(dim=1).values.sum().double() / total.double().clamp_min(1.0))
+    return cm, cm.argmax(dim=1), purity
+
+
 class KMeansModel(Model):
     _param_names = ("featuresCol", "predictionCol")
     featuresCol = "features"
@@ -102,11 +112,7 @@ class KMeansModel(Model):
         """(contingency int64 [k, num_classes] = rows of cluster c carrying label l, majority label per
         cluster [k], purity = the share of rows whose label is their cluster's majority label), taken
         through the confusion kernel of ``ops/metrics.py``."""
-        n = max(self.k, int(num_classes))
-        cm = OM.confusion_matrix(pred.to(self.device), y.to(self.device), n)[:self.k, :int(num_classes)]
-        total = cm.sum()
-        purity = float(cm.max(dim=1).values.sum().double() / total.double().clamp_min(1.0))
-        majority = cm.argmax(dim=1)
+        cm, majority, purity = cluster_label_map(self.k, self.device, pred, y, num_classes)
         self.majority_labels = [int(v) for v in majority.tolist()]
         return cm, majority, purity
 

@@ -31,6 +31,7 @@ STREAM_INIT = 3
 STREAM_FINDSPLITS = 4  # findSplits row sample (Bernoulli, keyed by global row id)
 STREAM_KMEANS_INIT = 5  # KMeans "random" init: one key per global row id, the k smallest keys win
 STREAM_KMEANS_PP = 6    # KMeans "k-means++": uniform j decides the j-th D^2 draw
+STREAM_GMM_INIT = 7     # GaussianMixture "random" init: as STREAM_KMEANS_INIT, its own keys
 STREAM_BOOTSTRAP_BASE = 0x1000  # + tree id
 STREAM_FEATURE_SUBSET = 0x7F000000  # per (tree,node) in counter
 

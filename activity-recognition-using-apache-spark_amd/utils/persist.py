@@ -136,6 +136,15 @@ def _build(md, t, children, device):
         m.predictionCol = p.get("predictionCol", m.predictionCol)
         m.feature_cols = st.get("feature_cols")
         return m
+    if cls == "GaussianMixtureModel":
+        from ..models.gmm import GaussianMixtureModel
+
+        m = GaussianMixtureModel.from_state(t, uid=uid, device=_dev(device))
+        m.featuresCol = p.get("featuresCol", m.featuresCol)
+        m.predictionCol = p.get("predictionCol", m.predictionCol)
+        m.probabilityCol = p.get("probabilityCol", m.probabilityCol)
+        m.feature_cols = st.get("feature_cols")
+        return m
     if cls == "HMMSmootherModel":
         from ..models.hmm import HMMSmootherModel
 

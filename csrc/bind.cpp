@@ -716,6 +716,70 @@ PYBIND11_MODULE(_har_native, m) {
     check(har_kmeans_update(&a, S(st)), "kmeans_update");
   });
 
+  // Gaussian mixtures (gmm.hip)
+  m.def("gmm_rows_per_block", []() { return har_gmm_rows_per_block(); });
+  m.def("gmm_group", [](int D, int K) {
+    const int g = har_gmm_group(D, K);
+    if (g < 0) check(g, "gmm_group");
+    return g;
+  });
+  m.def("gmm_grid", [](int64_t N, int D, int K, int max_blocks) {
+    const int g = har_gmm_grid(N, D, K, max_blocks);
+    if (g < 0) check(g, "gmm_grid");
+    return g;
+  });
+  m.def("gmm_estep", [](u Z, int64_t N, int D, int K, u mu, u W, u c, u w, u resp, u lse, u pred, u q, u slabs, u part,
+                        int max_blocks, u state, int max_iter, u wr, u st) {
+    GmmEstepArgs a{};
+    a.Z = P<const float>(Z);
+    a.N = N;
+    a.D = D;
+    a.K = K;
+    a.mu = P<const float>(mu);
+    a.W = P<const float>(W);
+    a.c = P<const float>(c);
+    a.w = P<const float>(w);
+    a.resp = P<float>(resp);
+    a.lse = P<float>(lse);
+    a.pred = P<int32_t>(pred);
+    a.q = P<float>(q);
+    a.slabs = P<float>(slabs);
+    a.part = P<double>(part);
+    a.max_blocks = max_blocks;
+    a.state = P<const int>(state);
+    a.max_iter = max_iter;
+    a.wr = P<float>(wr);
+    check(har_gmm_estep(&a, S(st)), "gmm_estep");
+  });
+  m.def("gmm_finish", [](u slabs, int nslab, int K, int D, int diag, int max_iter, double reg, u mu, u W, u c, u Nk, u pi,
+                         u state, u st) {
+    GmmFinishArgs a{};
+    a.slabs = P<const float>(slabs);
+    a.nslab = nslab;
+    a.K = K;
+    a.D = D;
+    a.diag = diag;
+    a.max_iter = max_iter;
+    a.reg = reg;
+    a.mu = P<float>(mu);
+    a.W = P<float>(W);
+    a.c = P<float>(c);
+    a.Nk = P<double>(Nk);
+    a.pi = P<double>(pi);
+    a.state = P<const int>(state);
+    check(har_gmm_finish(&a, S(st)), "gmm_finish");
+  });
+  m.def("gmm_control", [](u part, int npart, int max_iter, double tol, u state, u hist, u st) {
+    GmmControlArgs a{};
+    a.part = P<const double>(part);
+    a.npart = npart;
+    a.max_iter = max_iter;
+    a.tol = tol;
+    a.state = P<int>(state);
+    a.hist = P<double>(hist);
+    check(har_gmm_control(&a, S(st)), "gmm_control");
+  });
+
   m.def("grad_reduce_adam", [](std::vector<u> src, std::vector<int64_t> start, std::vector<int64_t> len,
                                std::vector<int64_t> lds, std::vector<int> nsl, int64_t n, u G, u param, u mm, u vv,
                                u pb, float lr, float b1, float b2, float eps, float wd, u step, int tick, int mode,

@@ -586,6 +586,72 @@ typedef struct KMeansUpdateArgs {
 } KMeansUpdateArgs;
 int har_kmeans_update(const KMeansUpdateArgs* a, hipStream_t s);
 
+// ---- Gaussian mixtures (gmm.hip): full-covariance EM on the fp32 matrix cores ----
+// Working rows Z [N][D] fp32 (standardised by the caller).  Component k: mu [K][D], the upper triangular
+// W_k = L_k^{-T} [K][D][D] (Sigma_k = L_k L_k^T; the kernel reads entries on and above the diagonal only)
+// and c [K] = log pi_k - D/2 log 2pi - sum_i log L_k[i][i] (-inf: the component is never chosen, r = 0).
+// q[n][k] = |(z_n - mu_k) W_k|^2, t = c_k - q / 2, lse = logsumexp_k t, r = exp(t - lse), pred = the first
+// argmax of r.  K in 1..har_gmm_max_k(), D in 1..har_gmm_max_d().  Contract codes as above (-2, -4).
+// The grid is persistent: har_gmm_grid(N, D, K, max_blocks) workgroups (independent of N beyond one per
+// har_gmm_rows_per_block() rows; max_blocks > 0 lowers the cap), each looping over row tiles, keeping
+// its moment accumulators in LDS across the tiles and storing ONE moment slab [K][1 + Dp + Dp Dp] (Dp = D
+// rounded up to 4) at its end: N_k | S1_k [Dp] | S2_k [Dp][Dp], moments of w r about mu_k, S2 valid for
+// i <= j only (the upper triangle), and one fp64 partial of sum_n w lse.  Components whose accumulators
+// do not fit the LDS together are taken har_gmm_group(D, K) at a time, one pass over the tiles per group;
+// the passes after the first read w r back from the scratch wr, which is then required.
+// No atomics: two launches give the same bits.
+typedef struct GmmEstepArgs {
+  const float* Z;
+  int64_t N;
+  int D, K;
+  const float* mu;
+  const float* W;
+  const float* c;
+  const float* w;   // [N] row weights >= 0 (nullable: 1)
+  float* resp;      // [N][K] (nullable)
+  float* lse;       // [N] (nullable)
+  int32_t* pred;    // [N] (nullable)
+  float* q;         // [N][K] (nullable)
+  float* slabs;     // [grid][K][1 + Dp + Dp Dp], overwritten (nullable: no moments)
+  float* wr;        // [N][K] scratch for w r (needed with slabs when har_gmm_group(D, K) < K, else nullable)
+  double* part;     // [grid] (nullable)
+  int max_blocks;   // 0: the default cap
+  const int* state; // [2] iterations, converged (nullable): no work when converged or iterations >= max_iter
+  int max_iter;
+} GmmEstepArgs;
+int har_gmm_estep(const GmmEstepArgs* a, hipStream_t s);
+int har_gmm_rows_per_block();
+int har_gmm_group(int D, int K);
+int har_gmm_grid(int64_t N, int D, int K, int max_blocks);
+// One workgroup per component, nothing when state (nullable) says converged or iterations >= max_iter.
+// Sums the slabs in order in fp64; delta = S1 / N_k, mu += delta, Sigma = S2 / N_k - delta delta^T + reg I
+// (diag: off-diagonal entries zeroed), pi_k = N_k / sum N, then the Cholesky factor, W = L^{-T} and c, all
+// in fp64 in LDS, written as fp32.  N_k = 0 or a non-positive / non-finite pivot: mu and W stay, c is
+// rebuilt from the kept factor's diagonal and the new weight.
+typedef struct GmmFinishArgs {
+  const float* slabs;
+  int nslab, K, D, diag, max_iter;
+  double reg;
+  float* mu;
+  float* W;
+  float* c;
+  double* Nk;        // [K]
+  double* pi;        // [K]
+  const int* state;  // [2] iterations, converged (nullable: always run)
+} GmmFinishArgs;
+int har_gmm_finish(const GmmFinishArgs* a, hipStream_t s);
+// One workgroup.  When not converged and iterations < max_iter: hist[iterations] = the sum of part[0 ..
+// npart) in the fixed order of har_kmeans_update's cost, converged = iterations > 0 and |loglik -
+// hist[iterations - 1]| <= tol, iterations += 1.  Otherwise nothing changes.
+typedef struct GmmControlArgs {
+  const double* part;
+  int npart, max_iter;
+  double tol;
+  int* state;
+  double* hist;  // [max_iter]
+} GmmControlArgs;
+int har_gmm_control(const GmmControlArgs* a, hipStream_t s);
+
 // ---- CSV on device (4 KiB chunks per workgroup) ----
 int har_csv_count_newlines(const uint8_t* buf, int64_t n, int32_t* counts, hipStream_t s);
 int har_csv_newline_pos(const uint8_t* buf, int64_t n, const int64_t* block_off, int64_t* pos, hipStream_t s);

@@ -107,6 +107,51 @@ def run_kmeans(cfg: RunConfig, dev, ctx, train, test, vocab, timer, log, main_ra
             "purity": purity, "contingency": cm.tolist(), "majority_labels": model.majority_labels}
 
 
+def run_gmm(cfg: RunConfig, dev, train, test, vocab, timer, log, main_rank) -> dict:
+    """``--gmm K``: a K-component Gaussian mixture on the training rows' dense numeric features (every rank
+    fits the whole table), then the block of result.txt — weights, sizes, log-likelihood, iterations, the
+    mean test log-likelihood, silhouette on the test rows, purity and the cluster-by-label table."""
+    from har.evaluation.evaluators import ClusteringEvaluator
+    from har.models.gmm import GaussianMixture
+    from har.models.kmeans import kmeans_feature_cols, table_features
+
+    cols = kmeans_feature_cols(cfg.encoding)
+    X_train, X_test = table_features(train, cols, dev), table_features(test, cols, dev)
+    y_train = torch.as_tensor(train["label"].data.astype(np.int64), device=dev)
+    est = GaussianMixture(k=cfg.gmm, maxIter=cfg.gmm_max_iter, covarianceType=cfg.gmm_cov, initMode=cfg.gmm_init,
+                          seed=cfg.seed, device=dev)
+    with timer.phase("fit:gmm"):
+        model = est.fit_tensors(X_train)
+    model.feature_cols = cols
+    train_s = round(timer.get("fit:gmm"), 6)
+    with timer.phase("evaluate:gmm"):
+        cm, majority, purity = model.label_map(model.summary.predictions.long(), y_train, len(vocab))
+        n_test = X_test.shape[0]
+        pred_test = model.predict(X_test)
+        test_ll = float(model.score_samples(X_test).mean()) if n_test else 0.0
+        sil = ClusteringEvaluator(device=dev).evaluate_tensors(X_test, pred_test, model.k) if n_test else 0.0
+    s = model.summary
+    section(log, "GaussianMixture")
+    log.print(f"{model} trained in {train_s} seconds ({X_train.shape[1]} features, {cfg.gmm_cov} covariances, "
+              f"init {cfg.gmm_init})")
+    log.print("Weights            = " + str([round(float(v), 6) for v in model.weights.tolist()]))
+    log.print("Cluster Sizes      = " + str(s.clusterSizes))
+    log.print("Log-Likelihood     = %g" % s.logLikelihood)
+    log.print("Iterations         = %d (converged: %s)" % (s.numIter, s.converged))
+    log.print("Mean LL / row (test) = %g" % test_ll)
+    log.print("Silhouette (test)  = %g" % sil)
+    log.print("Purity (train)     = %g" % purity)
+    log.print("Cluster x label (rows: clusters; columns: " + ", ".join(str(v) for v in vocab) + ")")
+    for c, row in enumerate(cm.tolist()):
+        log.print("  %3d -> %-12s %s" % (c, vocab[int(majority[c])], row))
+    if cfg.save_models and main_rank:
+        persist.save(model, os.path.join(cfg.save_models, "gmm"), labels=vocab)
+    return {"model": str(model), "k": model.k, "train_s": train_s, "log_likelihood": s.logLikelihood,
+            "num_iter": s.numIter, "converged": s.converged, "cluster_sizes": s.clusterSizes,
+            "weights": model.weights.tolist(), "test_mean_log_likelihood": test_ll, "silhouette": sil, "purity": purity,
+            "contingency": cm.tolist(), "majority_labels": model.majority_labels}
+
+
 def run(cfg: RunConfig, ctx=None) -> dict:
     dev = ctx.device if ctx is not None else resolve_device(None if cfg.device == "auto" else cfg.device)
     main_rank = ctx is None or ctx.is_main
@@ -183,6 +228,17 @@ def run(cfg: RunConfig, ctx=None) -> dict:
                 wk = KMeans(k=min(cfg.kmeans, Xs.shape[0]), maxIter=2, initMode=cfg.kmeans_init, seed=cfg.seed,
                             device=dev).fit_features(Xs)
                 ClusteringEvaluator(device=dev).evaluate_tensors(Xs, wk.predict(Xs), wk.k)
+                device_sync(dev)
+            if cfg.gmm:  # the mixture (and its k-means init / silhouette) code objects, on 256 rows and 2 iterations
+                from har.evaluation.evaluators import ClusteringEvaluator
+                from har.models.gmm import GaussianMixture
+                from har.models.kmeans import kmeans_feature_cols, table_features
+
+                Xs = table_features(train.head(min(256, train.count())), kmeans_feature_cols(cfg.encoding), dev)
+                wg = GaussianMixture(k=min(cfg.gmm, Xs.shape[0]), maxIter=2, covarianceType=cfg.gmm_cov,
+                                     initMode=cfg.gmm_init, seed=cfg.seed, device=dev).fit_tensors(Xs)
+                wg.score_samples(Xs)
+                ClusteringEvaluator(device=dev).evaluate_tensors(Xs, wg.predict(Xs), wg.k)
                 device_sync(dev)
         # not part of any "trained in" time below (the reference's timers exclude SparkContext start-up too)
         log.print("Device warm-up (HIP code objects, allocator) %.6f seconds" % timer.get("device_warmup"))
@@ -273,6 +329,9 @@ def run(cfg: RunConfig, ctx=None) -> dict:
     kmeans_rec = None
     if cfg.kmeans:
         kmeans_rec = run_kmeans(cfg, dev, ctx, train, test, vocab, timer, log, main_rank)
+    gmm_rec = None
+    if cfg.gmm:
+        gmm_rec = run_gmm(cfg, dev, train, test, vocab, timer, log, main_rank)
     if cfg.save_models and main_rank:
         persist.save(pipe_model, os.path.join(cfg.save_models, "pipeline"), labels=vocab)
         if smoother is not None:
@@ -293,6 +352,8 @@ def run(cfg: RunConfig, ctx=None) -> dict:
                "phases_s": {k: round(v, 6) for k, v in timer.as_dict().items()}}
     if kmeans_rec is not None:
         summary["kmeans"] = kmeans_rec
+    if gmm_rec is not None:
+        summary["gmm"] = gmm_rec
     csvout.append_jsonl(os.path.join(cfg.out_dir, "metrics.jsonl"), summary)
     log.close()
     if cfg.report:

@@ -81,6 +81,8 @@ def run(args) -> dict:
     table = encode(pipe, raw, args.handle_invalid)
     if type(model).__name__ == "KMeansModel":
         return run_kmeans(args, model, table, labels, dev, t0)
+    if type(model).__name__ == "GaussianMixtureModel":
+        return run_gmm(args, model, table, labels, dev, t0)
     X = features_tensor(table, "features", dev)
     device_sync(dev)
     t_ingest = time.perf_counter() - t0
@@ -194,10 +196,54 @@ def run_kmeans(args, model, table, labels, dev, t0) -> dict:
     return rec
 
 
+def run_gmm(args, model, table, labels, dev, t0) -> dict:
+    """``--model gmm``: the cluster id per row, its majority label when the saved model carries a label map,
+    the largest probability and the row's log-likelihood."""
+    from har.models.kmeans import table_features
+
+    X = table_features(table, model.feature_cols, dev)
+    device_sync(dev)
+    t_ingest = time.perf_counter() - t0
+    e = model._estep(X)  # warm-up (code objects, allocator)
+    device_sync(dev)
+    t1 = time.perf_counter()
+    for _ in range(args.repeat):
+        e = model._estep(X)
+    device_sync(dev)
+    t_pred = (time.perf_counter() - t1) / max(1, args.repeat)
+    n = X.shape[0]
+    pred = e.pred.long()
+    ll = model.score_samples(X)
+    rec = {"model": str(model), "rows": n, "device": str(dev), "ingest_encode_s": round(t_ingest, 6),
+           "predict_s": round(t_pred, 6), "predict_windows_per_s": n / max(t_pred, 1e-12),
+           "clusters_used": int(torch.unique(pred).numel()), "mean_log_likelihood": float(ll.mean()) if n else 0.0}
+    maj = model.majority_labels
+    if maj is not None and "label" in table.columns:
+        y = torch.as_tensor(table["label"].data.astype(np.int64), device=dev)
+        rec["majority_label_accuracy"] = float((torch.as_tensor(maj, device=dev)[pred] == y).double().mean())
+    if args.out:
+        p = pred.cpu().numpy()
+        top = e.resp.max(dim=1).values.cpu().numpy() if n else np.zeros(0)
+        lls = ll.cpu().numpy()
+        uid = table["UID"].data if "UID" in table.columns else None
+        with open(args.out, "w", newline="") as f:
+            w = csv.writer(f)
+            w.writerow(["row"] + (["UID"] if uid is not None else []) + ["cluster"]
+                       + (["majority_label", "label_name"] if maj is not None else []) + ["probability", "log_likelihood"])
+            for i in range(n):
+                extra = []
+                if maj is not None:
+                    k = maj[p[i]]
+                    extra = [k, labels[k] if labels and k < len(labels) else ""]
+                w.writerow([i] + ([int(uid[i])] if uid is not None else []) + [int(p[i])] + extra
+                           + [float(top[i]), float(lls[i])])
+    return rec
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="Batch inference from models saved by main.py --save-models")
     ap.add_argument("--models", required=True, help="directory written by main.py --save-models")
-    ap.add_argument("--model", default="rf", help="sub-directory name: lr, lrcv, dt, dtcv, rf, rfcv, nb, mlp, gbt, kmeans")
+    ap.add_argument("--model", default="rf", help="sub-directory name: lr, lrcv, dt, dtcv, rf, rfcv, nb, mlp, gbt, kmeans, gmm")
     ap.add_argument("--data", default=DEFAULT_WISDM)
     ap.add_argument("--out", default="")
     ap.add_argument("--device", default="auto")
