@@ -570,7 +570,6 @@ PYBIND11_MODULE(_har_native, m) {
                                   S(stream_)),
           "window_features_mlp");
   });
-  m.def("window_set_legacy", [](int on) { har_window_set_legacy(on); });
   m.def("window_features", [](u stream, int64_t n_samples, int axes, int window, int stride, int64_t n_windows,
                               float hz, int nbins, u out, int ld_out, u st) {
     check(har_window_features(P<const float>(stream), n_samples, axes, window, stride, n_windows, hz, nbins,

@@ -339,8 +339,6 @@ int har_window_features_mlp(const float* stream, int64_t n_samples, int axes, in
                             uint16_t* out, int ld_out, hipStream_t s);
 int har_window_features(const float* stream, int64_t n_samples, int axes, int window, int stride,
                         int64_t n_windows, float hz, int nbins, float* out, int ld_out, hipStream_t s);
-// Probe switch: 1 = the pre-v3 (per-sample LDS reads) window kernels only, 0 = default selection.
-void har_window_set_legacy(int on);
 
 // ---- spectral window features (spectral.hip): the DFT of every (window, axis) on the matrix cores ----
 // 11 features per axis — 8 band fractions, dominant frequency, centroid, entropy — laid out

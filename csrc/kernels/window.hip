@@ -4,21 +4,25 @@
 //
 // Input: stream [S][A] fp32 (sample-major, axes interleaved), windows of W samples every
 // `stride` samples.  Every feature is per axis or per axis triad (x, y, z), so the unit of work
-// is a GROUP = (window, triad): 16 lanes (one 16-lane row of a wave, four groups per wave) own
-// one group, lane `sub` taking samples t = sub, sub + 16, sub + 32, ...
+// is a GROUP = (window, triad), owned by 8 / 16 / 32 / 64 lanes of a wave.  Two kernels:
 //
-//   * a block stages the contiguous sample span of its windows (overlapping windows share the
-//     span) HBM -> LDS with 16-byte loads, eight in flight per thread;
-//   * pass 1 (sum, sum of squares, min, max) and pass 2 (|x - mean|, (x - mean)^2, the 10-bin
-//     distribution, peaks, resultant, triad covariances) read the group's samples from LDS —
-//     consecutive lanes read consecutive samples, A (odd) floats apart: conflict-free banks —
-//     and accumulate per lane with no per-sample masking except in the first and the last
-//     iterations (t = 0, t >= W - 1);
-//   * the distribution counts are packed 6 bits per bin in one 64-bit register per axis
-//     (one v_lshl_add_u64 per sample) and the local maxima as a shift register of flags,
-//     both flushed every 32 iterations; npk / first / last come from popcount / ctz / clz;
-//   * the 16-lane reductions are DPP butterflies (quad_perm, row_half_mirror, row_mirror):
-//     VALU moves, no LDS round trips.
+//   * window_features_reg_kernel, the register-resident kernel, takes every shape whose staged
+//     span fits the LDS (W <= 1984): a block stages the contiguous sample span of its windows
+//     (overlapping windows share the span) HBM -> LDS with 16-byte loads, every lane reads a
+//     contiguous run of its group's samples into registers once, and both passes — pass 1 (sum,
+//     sum of squares, min, max), pass 2 (|x - mean|, (x - mean)^2, the 10-bin distribution, peaks,
+//     resultant, triad covariances) — run on registers.  See the comment block above it.
+//   * window_features_fallback_kernel takes what that kernel cannot stage — long windows
+//     (W > 1984) and sparse strides (stride so much larger than W that one wave's span exceeds the
+//     LDS): one LDS image per window, 16 lanes per group, lane `sub` taking samples t = sub,
+//     sub + 16, sub + 32, ... from LDS in both passes, with no per-sample masking except in the
+//     first and the last iterations (t = 0, t >= W - 1).  Its distribution counts are packed
+//     6 bits per bin in one 64-bit register per axis (one v_lshl_add_u64 per sample) and the
+//     local maxima as a shift register of flags, both flushed every 32 iterations; npk / first /
+//     last come from popcount / ctz / clz.
+//
+// The reductions over a group are DPP butterflies (quad_perm, row_half_mirror, row_mirror; then the
+// row / half swaps for 32 and 64 lanes): VALU moves, no LDS round trips.
 //
 // Output row (F = 17*A + 4*(A/3) floats), WISDM-43 first for A = 3:
 //   [bins: A x 10][avg: A][peak ms: A][absdev: A][std: A][resultant: A/3]
@@ -33,9 +37,6 @@
 #include "common.h"
 #include "mlp_frag.h"
 #include "../har_kernels.h"
-
-// A/B switch for probes: the pre-v3 kernels only (window_features_kernel / _persistent_kernel)
-bool g_window_legacy = false;
 
 namespace {
 
@@ -52,9 +53,7 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 // quad_perm xor-1, quad_perm xor-2, then row_half_mirror (and row_mirror for 16 lanes): after
 // the quad steps every lane of a quad holds the quad's value, so the mirrors pair whole quads,
 // then whole half-rows.
-template <int CTRL> __device__ __forceinline__ int dpp_i(int v) {
-  return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, false);
-}
+using wops::dpp_i;
 template <int LPW, typename T, typename Op> __device__ __forceinline__ T rreduce(T v, Op op) {
   static_assert(LPW == 8 || LPW == 16, "window groups of 8 or 16 lanes");
   auto mv = [](T x, auto ctrl) {
@@ -68,23 +67,25 @@ template <int LPW, typename T, typename Op> __device__ __forceinline__ T rreduce
   if constexpr (LPW == 16) v = op(v, mv(v, std::integral_constant<int, 0x140>{}));  // row_mirror: half-row <-> half-row
   return v;
 }
-template <int LPW> __device__ __forceinline__ float rsum(float v) {
-  return rreduce<LPW, float>(v, [](float a, float b) { return a + b; });
+// the fallback kernel's groups: 16 lanes (one row of a wave, four groups per wave)
+constexpr int FLPW = 16;
+__device__ __forceinline__ float rsum(float v) {
+  return rreduce<FLPW, float>(v, [](float a, float b) { return a + b; });
 }
-template <int LPW> __device__ __forceinline__ uint32_t rsumu(uint32_t v) {
-  return rreduce<LPW, uint32_t>(v, [](uint32_t a, uint32_t b) { return a + b; });
+__device__ __forceinline__ uint32_t rsumu(uint32_t v) {
+  return rreduce<FLPW, uint32_t>(v, [](uint32_t a, uint32_t b) { return a + b; });
 }
-template <int LPW> __device__ __forceinline__ float rmin(float v) {
-  return rreduce<LPW, float>(v, [](float a, float b) { return fminf(a, b); });
+__device__ __forceinline__ float rmin(float v) {
+  return rreduce<FLPW, float>(v, [](float a, float b) { return fminf(a, b); });
 }
-template <int LPW> __device__ __forceinline__ float rmax(float v) {
-  return rreduce<LPW, float>(v, [](float a, float b) { return fmaxf(a, b); });
+__device__ __forceinline__ float rmax(float v) {
+  return rreduce<FLPW, float>(v, [](float a, float b) { return fmaxf(a, b); });
 }
-template <int LPW> __device__ __forceinline__ int rmini(int v) {
-  return rreduce<LPW, int>(v, [](int a, int b) { return min(a, b); });
+__device__ __forceinline__ int rmini(int v) {
+  return rreduce<FLPW, int>(v, [](int a, int b) { return min(a, b); });
 }
-template <int LPW> __device__ __forceinline__ int rmaxi(int v) {
-  return rreduce<LPW, int>(v, [](int a, int b) { return max(a, b); });
+__device__ __forceinline__ int rmaxi(int v) {
+  return rreduce<FLPW, int>(v, [](int a, int b) { return max(a, b); });
 }
 
 // MLP = true: the training-input variant — every feature is written as bf16
@@ -147,7 +148,7 @@ __device__ __forceinline__ void pass2_step(const float* img, int t, int W, const
 }
 
 // fold the packed counts and peak bits of the n-iteration chunk starting at kbase
-template <int LPW> __device__ __forceinline__ void pass2_flush(Pass2Acc& a, int sub, int kbase, int n) {
+__device__ __forceinline__ void pass2_flush(Pass2Acc& a, int sub, int kbase, int n) {
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     const uint64_t h = a.h[c];
@@ -157,8 +158,8 @@ template <int LPW> __device__ __forceinline__ void pass2_flush(Pass2Acc& a, int 
     a.h[c] = 0;
     const uint32_t pk = a.pk[c];
     a.npk[c] += __builtin_popcount(pk);
-    const int f = sub + LPW * (kbase + n - 1 - (31 - __builtin_clz(pk | 1u)));  // oldest flag: highest bit
-    const int l = sub + LPW * (kbase + n - 1 - __builtin_ctz(pk | 0x80000000u));  // newest: lowest bit
+    const int f = sub + FLPW * (kbase + n - 1 - (31 - __builtin_clz(pk | 1u)));  // oldest flag: highest bit
+    const int l = sub + FLPW * (kbase + n - 1 - __builtin_ctz(pk | 0x80000000u));  // newest: lowest bit
     a.first[c] = pk ? min(a.first[c], f) : a.first[c];
     a.last[c] = pk ? max(a.last[c], l) : a.last[c];
     a.pk[c] = 0;
@@ -167,20 +168,20 @@ template <int LPW> __device__ __forceinline__ void pass2_flush(Pass2Acc& a, int 
 
 // The statistics of every (window, triad) group of one staged batch: `img0` holds windows
 // w0 .. w0 + nwin - 1, `pitch` floats apart.
-template <int A, int LPW, bool MLP>
+template <int A, bool MLP>
 __device__ __forceinline__ void window_groups(const float* img0, int64_t w0, int nwin, int W, int pitch,
                                               float ms_per_sample, float* __restrict__ out, int ld_out,
                                               const MlpOut& mo) {
-  constexpr int T3 = A / 3, GPW = 64 / LPW;
+  constexpr int T3 = A / 3, GPW = 64 / FLPW;
   const int tid = (int)threadIdx.x;
-  const int lane = tid & 63, sub = lane % LPW;
+  const int lane = tid & 63, sub = lane % FLPW;
   const int wave = tid >> 6, g = wave % T3;
-  const int wi = GPW * (wave / T3) + lane / LPW;
+  const int wi = GPW * (wave / T3) + lane / FLPW;
   const bool valid = wi < nwin;
   const int64_t win = w0 + (valid ? wi : 0);
   const float* img = img0 + (valid ? wi : 0) * pitch + 3 * g;  // the group's triad: A floats per sample
-  const int C = (W + LPW - 1) / LPW;  // iterations (samples per lane, the last partial)
-  const int kfull = (W - 1) / LPW;    // k < kfull: every t = sub + LPW k lies in [0, W - 2]
+  const int C = (W + FLPW - 1) / FLPW;  // iterations (samples per lane, the last partial)
+  const int kfull = (W - 1) / FLPW;    // k < kfull: every t = sub + FLPW k lies in [0, W - 2]
   const float invW = 1.f / (float)W;
 
   // ---- pass 1: sum, sum of squares, min, max ----
@@ -192,7 +193,7 @@ __device__ __forceinline__ void window_groups(const float* img0, int64_t w0, int
     const float* p = img + sub * A;
     int k = 0;
 #pragma unroll 2
-    for (; k < kfull; ++k, p += LPW * A) {
+    for (; k < kfull; ++k, p += FLPW * A) {
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
         const float v = p[c];
@@ -200,7 +201,7 @@ __device__ __forceinline__ void window_groups(const float* img0, int64_t w0, int
       }
     }
     for (; k < C; ++k) {
-      const int t = sub + LPW * k;
+      const int t = sub + FLPW * k;
       const bool ok = t < W;
       const float* pp = img + (ok ? t : W - 1) * A;  // a duplicate of a window sample: min / max unchanged
 #pragma unroll
@@ -211,8 +212,8 @@ __device__ __forceinline__ void window_groups(const float* img0, int64_t w0, int
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      mean[c] = rsum<LPW>(s[c]) * invW; en[c] = rsum<LPW>(q[c]) * invW;
-      mn[c] = rmin<LPW>(lo[c]); mx[c] = rmax<LPW>(hi[c]);
+      mean[c] = rsum(s[c]) * invW; en[c] = rsum(q[c]) * invW;
+      mn[c] = rmin(lo[c]); mx[c] = rmax(hi[c]);
     }
   }
 
@@ -235,14 +236,14 @@ __device__ __forceinline__ void window_groups(const float* img0, int64_t w0, int
   int k = 1;
 #pragma unroll 2
   for (; k < kfull; ++k) {
-    pass2_step<A, false>(img, sub + LPW * k, W, K, a);
-    if ((k & 31) == 31) pass2_flush<LPW>(a, sub, k - 31, 32);
+    pass2_step<A, false>(img, sub + FLPW * k, W, K, a);
+    if ((k & 31) == 31) pass2_flush(a, sub, k - 31, 32);
   }
   for (; k < C; ++k) {
-    pass2_step<A, true>(img, sub + LPW * k, W, K, a);
-    if ((k & 31) == 31) pass2_flush<LPW>(a, sub, k - 31, 32);
+    pass2_step<A, true>(img, sub + FLPW * k, W, K, a);
+    if ((k & 31) == 31) pass2_flush(a, sub, k - 31, 32);
   }
-  if (C & 31) pass2_flush<LPW>(a, sub, C & ~31, C & 31);
+  if (C & 31) pass2_flush(a, sub, C & ~31, C & 31);
 
   // ---- reduce + write ----
   float* o = MLP ? nullptr : out + win * (int64_t)ld_out;
@@ -259,7 +260,7 @@ __device__ __forceinline__ void window_groups(const float* img0, int64_t w0, int
   constexpr int F = 17 * A + 4 * T3;
   if constexpr (MLP) {  // zero the pad columns of the row (triad 0's group)
     if (g == 0)
-      for (int f = F + sub; f < ld_out; f += LPW)
+      for (int f = F + sub; f < ld_out; f += FLPW)
         if (valid) ob[f] = 0;
   }
   const int off_avg = A * NB, off_peak = off_avg + A, off_abs = off_peak + A, off_std = off_abs + A;
@@ -272,26 +273,22 @@ __device__ __forceinline__ void window_groups(const float* img0, int64_t w0, int
     // a constant axis (max == min) has exactly zero spread: its fp32 mean need not equal the sample, so
     // the deviation sums need not cancel (a clipped, saturated sensor gave correlations of +-1 for 0)
     const bool flat = !(mx[c] > mn[c]);
-    const float ad = flat ? 0.f : rsum<LPW>(a.ad[c]) * invW;
-    const float var = rsum<LPW>(a.v2[c]) * invW;
+    const float ad = flat ? 0.f : rsum(a.ad[c]) * invW;
+    const float var = rsum(a.v2[c]) * invW;
     sd[c] = flat ? 0.f : __builtin_amdgcn_sqrtf(var);
-    const int npk = (int)rsumu<LPW>((uint32_t)a.npk[c]);
-    const int first = rmini<LPW>(a.first[c]), last = rmaxi<LPW>(a.last[c]);
-    // bins: lane `sub` writes bin `sub` (and lanes 0, 1 of 8-lane groups bins 8, 9); the word is
-    // picked by a select chain, not an indexed register array
+    const int npk = (int)rsumu((uint32_t)a.npk[c]);
+    const int first = rmini(a.first[c]), last = rmaxi(a.last[c]);
+    // bins: lane `sub` writes bin `sub`; the word is picked by a select chain, not an indexed
+    // register array
     uint32_t hw[5];
 #pragma unroll
-    for (int j = 0; j < 5; ++j) hw[j] = rsumu<LPW>(a.hw[c][j]);
+    for (int j = 0; j < 5; ++j) hw[j] = rsumu(a.hw[c][j]);
     {
       uint32_t word = hw[0];
 #pragma unroll
       for (int j = 1; j < 5; ++j) word = (sub >> 1) == j ? hw[j] : word;
       const uint32_t cnt = (sub & 1) ? word >> 16 : word & 0xffffu;
       emit(sub < NB, ax * NB + sub, (float)cnt * invW);
-    }
-    if constexpr (LPW < NB) {
-      const uint32_t cnt = (sub & 1) ? hw[4] >> 16 : hw[4] & 0xffffu;
-      emit(sub < NB - LPW, ax * NB + LPW + sub, (float)cnt * invW);
     }
     // scalars: lanes 0..6
     const float peak =
@@ -308,8 +305,8 @@ __device__ __forceinline__ void window_groups(const float* img0, int64_t w0, int
   }
   // triad: resultant (lane 0) and the three correlations (lanes 1..3)
   {
-    const float res = rsum<LPW>(a.res) * invW;
-    const float cxy = rsum<LPW>(a.cxy) * invW, cxz = rsum<LPW>(a.cxz) * invW, cyz = rsum<LPW>(a.cyz) * invW;
+    const float res = rsum(a.res) * invW;
+    const float cxy = rsum(a.cxy) * invW, cxz = rsum(a.cxz) * invW, cyz = rsum(a.cyz) * invW;
     const float rxy = (sd[0] > 0.f && sd[1] > 0.f) ? cxy * __builtin_amdgcn_rcpf(sd[0] * sd[1]) : 0.f;
     const float rxz = (sd[0] > 0.f && sd[2] > 0.f) ? cxz * __builtin_amdgcn_rcpf(sd[0] * sd[2]) : 0.f;
     const float ryz = (sd[1] > 0.f && sd[2] > 0.f) ? cyz * __builtin_amdgcn_rcpf(sd[1] * sd[2]) : 0.f;
@@ -322,18 +319,21 @@ __device__ __forceinline__ void window_groups(const float* img0, int64_t w0, int
   }
 }
 
+// The fallback for what the register-resident kernel below cannot stage: long windows (W > 1984) and
+// sparse strides (the contiguous span of one wave's windows exceeds the LDS).  Every window gets its
+// own LDS image, so neither the stride nor a shared span bounds it: four images per axis triad must
+// fit the 160 KB LDS, else the launcher returns contract code -5.
 // One block = `waves` waves = 4 * waves groups = 4 * waves / (A / 3) whole windows (host picks
 // `waves` as a multiple of A / 3).  Wave v takes triad v % (A / 3) of the four windows
-// 4 (v / (A / 3)) .. + 3, one per row.  Every window gets its own LDS image, `pitch` floats apart:
+// 4 (v / (A / 3)) .. + 3, one per row.  The images lie `pitch` floats apart:
 // with pitch = 16 A (mod 64) dwords the four rows of a wave (same triad, consecutive images)
 // read disjoint bank sets — lane banks A * sub + r * pitch are distinct over the 64 lanes for odd A
 // (the host picks the pitch).  One-shot: stage, compute, write.
-template <int A, int LPW, bool MLP>
-__global__ __launch_bounds__(256) void window_features_kernel(const float* __restrict__ stream, int64_t n_samples,
-                                                              int W, int stride, int64_t n_windows,
-                                                              float ms_per_sample, float* __restrict__ out,
-                                                              int ld_out, MlpOut mo, int pitch) {
-  constexpr int T3 = A / 3, GPW = 64 / LPW;  // groups per wave
+template <int A, bool MLP>
+__global__ __launch_bounds__(256) void window_features_fallback_kernel(
+    const float* __restrict__ stream, int64_t n_samples, int W, int stride, int64_t n_windows, float ms_per_sample,
+    float* __restrict__ out, int ld_out, MlpOut mo, int pitch) {
+  constexpr int T3 = A / 3, GPW = 64 / FLPW;  // groups per wave
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int nt = (int)blockDim.x, tid = (int)threadIdx.x;
   const int wpb = (nt >> 6) * GPW / T3;
@@ -385,94 +385,7 @@ __global__ __launch_bounds__(256) void window_features_kernel(const float* __res
   }
   __syncthreads();
 
-  window_groups<A, LPW, MLP>(img0, w0, nwin, W, pitch, ms_per_sample, out, ld_out, mo);
-}
-
-// Persistent variant (16-byte aligned window starts): each block walks batches b, b + grid, ...
-// of `wpb` windows.  The NEXT batch is loaded into NR float4 registers per thread while the
-// current one is computed from LDS, so the HBM latency of a batch hides behind the statistics of
-// the previous one instead of being paid by every block up front (one-shot blocks: stage, then
-// compute, with only four or two blocks per CU).  Loads are unconditional (clamped into the
-// stream) so their waits stay counted; the host picks NR >= float4s per batch / threads.
-template <int A, int LPW, bool MLP, int NR>
-__global__ __launch_bounds__(256) void window_features_persistent_kernel(
-    const float* __restrict__ stream, int64_t n_samples, int W, int stride, int64_t n_windows, float ms_per_sample,
-    float* __restrict__ out, int ld_out, MlpOut mo, int pitch) {
-  constexpr int T3 = A / 3, GPW = 64 / LPW;
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int nt = (int)blockDim.x, tid = (int)threadIdx.x;
-  const int wpb = (nt >> 6) * GPW / T3;
-  const int64_t nbatch = (n_windows + wpb - 1) / wpb;
-  float* img0 = lds + PAD;
-  v4f* d4 = reinterpret_cast<v4f*>(img0);
-  const int n = W * A, n4 = (n + 3) >> 2, p4 = pitch >> 2, gs4 = stride * A >> 2;
-  // non-overlapping windows with unpadded images: float4 f of a batch is float4 f of its image
-  // span in the stream AND in LDS — no (window, offset) split per float4
-  const bool flat = stride == W && pitch == n;
-  const int64_t t4 = n_samples * A >> 2;  // whole float4s of the stream
-  const v4f* s4 = reinterpret_cast<const v4f*>(stream);
-  const uint32_t magic = 0xffffffffu / (uint32_t)n4 + 1u;  // f / n4 = umulhi(f, magic) for f * n4 < 2^32
-  const int totmax = wpb * n4;
-  int64_t b = blockIdx.x;
-  if (b >= nbatch) return;  // block-uniform; no barrier reached
-  // (stream, LDS) float4 offsets of this thread's u-th float4 of a batch; slots past the batch
-  // re-load slot 0 (cache hits).  Recomputed per use behind an opaque copy of tid: held, they
-  // would cost two VGPRs per float4.
-  int tid_ = tid;
-  auto offs = [&](int u, int& rel, int& di) {
-    const int f0 = tid_ + u * nt, f = f0 < totmax ? f0 : tid_;
-    if (flat) {
-      rel = f; di = f;
-    } else {
-      const int i = (int)__umulhi((uint32_t)f, magic), j = f - i * n4;
-      rel = i * gs4 + j; di = i * p4 + j;
-    }
-  };
-  auto base = [&](int64_t batch, int& rlim) {
-    const int64_t g40 = batch * wpb * (int64_t)stride * A >> 2;
-    rlim = (int)min<int64_t>(t4 - g40, 0x7fffffff);
-    return s4 + g40;
-  };
-  v4f r[NR];
-  {
-    asm volatile("" : "+v"(tid_));
-    int rlim;
-    const v4f* sb = base(b, rlim);
-#pragma unroll
-    for (int u = 0; u < NR; ++u) {
-      int rel, di;
-      offs(u, rel, di);
-      r[u] = sb[rel < rlim ? rel : rlim - 1];  // unconditional (clamped) loads: counted waits
-    }
-  }
-  for (; b < nbatch; b += gridDim.x) {
-    const int64_t w0 = b * wpb;
-    const int nwin = (int)min<int64_t>(wpb, n_windows - w0);
-    const int tot = nwin * n4;
-    const bool more = b + gridDim.x < nbatch;
-    {
-      asm volatile("" : "+v"(tid_));
-      int rlim, rlim_n;
-      base(b, rlim);
-      const v4f* sbn = base(more ? b + gridDim.x : b, rlim_n);
-      // store this batch's float4 u, then reuse its registers for the next batch's float4 u (the
-      // last batch re-loads itself: cache hits)
-#pragma unroll
-      for (int u = 0; u < NR; ++u) {
-        int rel, di;
-        offs(u, rel, di);
-        if (tid + u * nt < tot && rel < rlim) d4[di] = r[u];
-        r[u] = sbn[rel < rlim_n ? rel : rlim_n - 1];  // unconditional: a conditional load would drain vmcnt
-      }
-      // floats past the stream's last whole float4 (n_samples * A % 4 != 0): the last window only
-      const int64_t last0 = (w0 + nwin - 1) * stride * A;
-      for (int64_t e = max(t4 * 4, last0) + tid; e < last0 + n; e += nt)
-        img0[(nwin - 1) * pitch + (e - last0)] = stream[e];
-    }
-    __syncthreads();
-    window_groups<A, LPW, MLP>(img0, w0, nwin, W, pitch, ms_per_sample, out, ld_out, mo);
-    __syncthreads();  // every wave is done with the images before they are overwritten
-  }
+  window_groups<A, MLP>(img0, w0, nwin, W, pitch, ms_per_sample, out, ld_out, mo);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -552,7 +465,7 @@ __device__ __forceinline__ void flag_step(uint32_t& R, uint32_t& PT, float x, fl
       : "scc");
 }
 
-// bin of a sample: (x - lo) * (10 / range) in fp32, the legacy kernel's arithmetic (x >= lo, so the
+// bin of a sample: (x - lo) * (10 / range) in fp32, the fallback kernel's arithmetic (x >= lo, so the
 // conversion never sees a negative), clamped to bin 9.  (The one-fma form x sc + (-lo sc), one VALU less
 // per sample and axis, moved boundary samples of quantized sensor data — WISDM's 2-decimal readings sit
 // exactly on bin edges — off the float64 definition's bins: tests/test_raw.py; rejected)
@@ -562,24 +475,15 @@ __device__ __forceinline__ uint32_t bin_of(float x, float sc, float lo) {
   return b < (uint32_t)(NB - 1) ? b : (uint32_t)(NB - 1);
 }
 
-// P32: non-overlapping windows (stride == W) with 32-sample runs (C = 32, even): every window gets its
-// own LDS image with a 4-float pad after each 32 samples (sample t at t A + 4 (t >> 5)), so the lanes of a
-// group, 32 A + 4 floats apart, still read distinct banks (an unpadded 32 A stride would put 16 lanes on
-// 2 - 4 banks).  The pads keep every float4 of the copy 16-byte aligned (32 A is a multiple of 4).  It
-// lets a 500-sample 9-axis window run on 16-lane groups (16 x 32 >= 500) instead of 32 x 17.
-__host__ __device__ constexpr int p32_pos(int t, int A) { return t * A + 4 * (t >> 5); }
-__host__ __device__ inline int p32_pitch(int W, int A) { return (p32_pos(W, A) + 4 + 3) & ~3; }
-
 // The statistics of one staged batch (windows w0 .. w0 + nwin - 1, their samples at `span`, `ip` floats
 // per window image): each lane reads its run into registers, then both passes, the reductions and the
 // row write.
-template <int A, int LPW, bool MLP, int RCMAX, bool P32, bool FIXC>
+template <int A, int LPW, bool MLP, int RCMAX, bool FIXC>
 __device__ __forceinline__ void reg_window_batch(const float* span, int64_t w0, int nwin, int W, int ip, int C,
                                                  float ms_per_sample, float* __restrict__ out, int ld_out,
                                                  const MlpOut& mo, const float* nrm) {
   constexpr int T3 = A / 3, GPW = 64 / LPW;
   const int tid = (int)threadIdx.x;
-  auto pos = [&](int t) { return P32 ? p32_pos(t, A) : t * A; };
   const int lane = tid & 63;
   const int wave = tid >> 6, sub = lane % LPW;
   const int g = wave % T3;
@@ -598,24 +502,22 @@ __device__ __forceinline__ void reg_window_batch(const float* span, int64_t w0, 
   // FIXC: the run read unclamped from one base address (immediate LDS offsets — the clamped form cost a
   // 24-bit multiply, a min and a 64-bit address multiply-add per sample); run positions past W - 1 read
   // the span's next samples or its slack (sized by the launcher) and get the copies of sample W - 1 below
-  constexpr bool FLAT = FIXC && !P32;
 #pragma unroll
   for (int k = 0; k < RCMAX; ++k)
     if (k < C) {
-      const float* p = FLAT ? img + (tb + k) * A : img + pos(min(tb + k, W - 1));
+      const float* p = FIXC ? img + (tb + k) * A : img + min(tb + k, W - 1) * A;
 #pragma unroll
       for (int c = 0; c < 3; ++c) x[c][k] = p[c];
     }
   float xl[3], pv0[3];
   {
-    const float* pl = img + pos(W - 1);
-    // sample before the run (t = -1: the PAD / previous window; P32: sample 0 — lane 0's t = 0 peak
-    // bit is masked either way)
-    const float* pp = img + (P32 ? pos(max(min(tb, W) - 1, 0)) : (min(tb, W) - 1) * A);
+    const float* pl = img + (W - 1) * A;
+    // sample before the run (t = -1: the PAD / previous window — lane 0's t = 0 peak bit is masked)
+    const float* pp = img + (min(tb, W) - 1) * A;
 #pragma unroll
     for (int c = 0; c < 3; ++c) { xl[c] = pl[c]; pv0[c] = pp[c]; }
   }
-  if constexpr (FLAT) {
+  if constexpr (FIXC) {
     if (LPW * RCMAX != W) {  // (uniform: runs that overhang the window; none at W = LPW C)
 #pragma unroll
       for (int k = 0; k < RCMAX; ++k) {
@@ -819,7 +721,7 @@ __device__ __forceinline__ void reg_window_batch(const float* span, int64_t w0, 
 // 1-wave blocks vs 63 us one-shot at 131k windows, and 1.3x slower at 1.3M; and a register-prefetch
 // persistent variant — the next span's 10 float4 per thread loaded right after the runs are read, stored to
 // LDS after pass 2, 168 VGPRs at 3 waves per SIMD, no spills — 73 vs 62 us: one-shot blocks it is.)
-template <int A, int LPW, bool MLP, int RCMAX, bool P32 = false, int WPE = 1, bool FIXC = false>
+template <int A, int LPW, bool MLP, int RCMAX, int WPE = 1, bool FIXC = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void window_features_reg_kernel(const float* __restrict__ stream, int W,
                                                                   int stride, int64_t n_windows, float ms_per_sample,
                                                                   float* __restrict__ out, int ld_out, MlpOut mo,
@@ -836,18 +738,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
     constexpr int F = 17 * A + 4 * (A / 3);
     for (int f = tid; f < 2 * F; f += nt) lds[f] = f < F ? mo.mean[f] : mo.inv_std[f - F];
   }
-  // image pitch (floats) between consecutive windows: P32 images, padded images (ipw > 0, non-overlapping
+  // image pitch (floats) between consecutive windows: padded images (ipw > 0, non-overlapping
   // windows: a pitch of 16 mod 32 floats puts the two 16-lane windows of a 32-lane LDS bank group on
   // disjoint banks — the contiguous 600-float pitch of W = 200 x 3 axes had 32% bank-conflict cycles,
   // profiles/r5/window_pmc.md), or the shared span (stride A floats per window)
-  const int ip = P32 ? p32_pitch(W, A) : ipw > 0 ? ipw : stride * A;
+  const int ip = ipw > 0 ? ipw : stride * A;
 
   const int64_t w0 = (int64_t)blockIdx.x * wpb;
   const int nwin = (int)min<int64_t>(wpb, n_windows - w0);
   // float4 loads in flight per thread while staging: 12 — a 4-wave block's ~2,470-float4 span (the
   // 200-sample shapes) is then ONE round of loads instead of two dependent ones
   constexpr int SU = 12;
-  if (P32 || ipw > 0) {  // ---- stage the windows, one padded image each (float4 granules) ----
+  if (ipw > 0) {  // ---- stage the windows, one padded image each (float4 granules) ----
     const v4f* s4 = reinterpret_cast<const v4f*>(stream + w0 * (int64_t)W * A);
     const int n4w = W * A / 4, n4 = nwin * n4w;
     const uint32_t magic = 0xffffffffu / (uint32_t)n4w + 1u;  // f / n4w = umulhi(f, magic) for f * n4w < 2^32
@@ -858,7 +760,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
 #pragma unroll
       for (int u = 0; u < SU; ++u) {
         const int f = min(f0 + u * nt, n4 - 1), wl = (int)__umulhi((uint32_t)f, magic), e = 4 * (f - wl * n4w);
-        *reinterpret_cast<v4f*>(span + wl * ip + e + (P32 ? 4 * (e / (32 * A)) : 0)) = r[u];
+        *reinterpret_cast<v4f*>(span + wl * ip + e) = r[u];
       }
     }
   } else {
@@ -886,125 +788,54 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
   }
   }
   __syncthreads();
-  reg_window_batch<A, LPW, MLP, RCMAX, P32, FIXC>(span, w0, nwin, W, ip, C, ms_per_sample, out, ld_out, mo,
-                                                 MLP ? lds : nullptr);
-}
-
-int cu_count() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) !=
-                                                 hipSuccess || n <= 0)
-      n = 256;
-  }
-  return n;
+  reg_window_batch<A, LPW, MLP, RCMAX, FIXC>(span, w0, nwin, W, ip, C, ms_per_sample, out, ld_out, mo,
+                                            MLP ? lds : nullptr);
 }
 
 template <int A, bool MLP>
 int launch_axes(const float* stream, int64_t n_samples, int window, int stride, int64_t n_windows, float ms,
                 float* out, int ld_out, MlpOut mo, hipStream_t s) {
   constexpr int T3 = A / 3;
-  // image pitch: 16 A (mod 64) dwords for odd A (conflict-free rows, see the kernel); 32 (mod 64)
-  // for A = 6 (even A only ever reaches even banks: rows one image apart stay disjoint)
-  const int n = window * A;
-  // do the 64 lanes of a wave (rows one image apart, lanes A floats apart) hit 64 distinct banks?
-  auto conflict_free = [&](int lpw, int pitch) {
-    uint64_t seen = 0;
-    for (int l = 0; l < 64; ++l) {
-      const uint64_t bit = 1ull << (((l / lpw) * pitch + (l % lpw) * A) & 63);
-      if (seen & bit) return false;
-      seen |= bit;
-    }
-    return true;
-  };
-  auto pitch_for = [&](int lpw) {
-    // contiguous images (flat staging, see the persistent kernel) unless that costs bank conflicts
-    if (stride == window && n % 4 == 0 && (conflict_free(lpw, n) || A % 2 == 0)) return n;
-    const int want = (A % 2) ? (lpw * A) % 64 : 32;
-    return n + (((want - n) % 64) + 64) % 64;
-  };
-  auto lds_bytes = [&](int wpb, int pitch) -> int64_t {
-    return (PAD + (int64_t)wpb * pitch + SLACK) * (int64_t)sizeof(float);
-  };
-  const bool vec = (reinterpret_cast<uintptr_t>(stream) & 15) == 0 && ((int64_t)stride * A) % 4 == 0;
-  // one block's launch: persistent + register-prefetched when the window starts are 16-byte
-  // aligned and a batch fits 24 float4 registers per thread (two waves per SIMD), else one-shot
-  auto launch = [&](auto lpw_c, int waves, int pitch) -> int {
-    constexpr int LPW = decltype(lpw_c)::value;
-    const int wpb = waves * (64 / LPW) / T3, nt = 64 * waves;
-    const int64_t bytes = lds_bytes(wpb, pitch);
-    const int64_t nbatch = (n_windows + wpb - 1) / wpb;
-    const int per = (int)((wpb * (int64_t)((n + 3) / 4) + nt - 1) / nt);  // float4s per thread per batch
-    if (vec && per <= 24 && (int64_t)stride * A * wpb < 0x7fffffff) {
-      const int64_t resident = std::max<int64_t>(1, std::min<int64_t>(8, (160 * 1024) / bytes));
-      const unsigned grid = (unsigned)std::min<int64_t>(nbatch, resident * cu_count());
-#define HAR_WIN_P(NR)                                                                              \
-  window_features_persistent_kernel<A, LPW, MLP, NR><<<grid, nt, (size_t)bytes, s>>>(              \
-      stream, n_samples, window, stride, n_windows, ms, out, ld_out, mo, pitch)
-      if (per <= 8) HAR_WIN_P(8);
-      else if (per <= 16) HAR_WIN_P(16);
-      else HAR_WIN_P(24);
-#undef HAR_WIN_P
-    } else {
-      window_features_kernel<A, LPW, MLP><<<(unsigned)nbatch, nt, (size_t)bytes, s>>>(
-          stream, n_samples, window, stride, n_windows, ms, out, ld_out, mo, pitch);
-    }
-    HAR_CHECK_LAUNCH();
-    return 0;
-  };
-  // register-resident kernel: the smallest group (8 / 16 / 32 / 64 lanes) whose runs of C <= RCMAX
-  // samples (C odd: lanes C*A floats apart hit distinct LDS banks for odd A) cover the window
-  if (!g_window_legacy) {
-    // the smallest group (8 / 16 / 32 / 64 lanes), then the shortest odd run C <= 31 (lanes C*A
-    // floats apart hit distinct LDS banks for odd A) with LPW * C >= W (W <= 1984): the fewer lanes
-    // per window, the fewer cross-lane reductions per sample (~a third of the VALU at 32 lanes)
-    // (8-lane groups only for overlapping windows: their span is shared, so the LDS per window — which
-    // bounds the waves per CU — stays small; measured: W = 200 stride 100 69 vs 77 us, stride 200 54
-    // vs 47 us with 8- vs 16-lane groups; round 6 with fixed-length runs, stride 100: 64 vs 77.5 us)
-    int lpw = 0, C = 0;
-    for (int l = stride < window ? 8 : 16; l <= 64 && !lpw; l *= 2)
-      for (int c = 5; c <= RCMAX_LONG; c += 2)
-        if (l * c >= window) { lpw = l; C = c; break; }
-    // non-overlapping windows of (16 x 31, 16 x 32] samples: 16-lane groups of 32-sample runs on padded
-    // per-window images (P32) instead of 32-lane groups (fewer cross-lane reductions per window).  Opt-in
-    // (HAR_WINDOW_P32=1): measured 364 vs 328 us on the 9-axis 500-sample shape — four windows' images per
-    // 3-wave block (73 KB) halve the resident waves, which costs more than the saved reductions
-    static const bool p32_on = [] {
-      const char* e = std::getenv("HAR_WINDOW_P32");
-      return e && std::atoi(e) != 0;
-    }();
-    const bool p32 = p32_on && stride == window && (window * A) % 4 == 0 &&
-                     (reinterpret_cast<uintptr_t>(stream) & 15) == 0 && lpw > 16 && window <= 16 * 32;
-    if (p32) { lpw = 16; C = 32; }
-    if (lpw) {
-      const int gpw = 64 / lpw;
-      // non-overlapping 16-lane windows: padded images, pitch = 16 (mod 32) floats (see the kernel)
-      const bool pimg = !p32 && lpw == 16 && A % 2 == 1 && stride == window && (window * A) % 4 == 0 &&
-                        (reinterpret_cast<uintptr_t>(stream) & 15) == 0 && (window * A) % 32 != 16 &&
-                        !std::getenv("HAR_WINDOW_NOPAD");
-      const int ipw = pimg ? window * A + (((16 - window * A) % 32) + 32) % 32 : 0;
-      // (the fixed-length runs read D = lpw C - window samples past the last window unclamped)
-      const bool fixc = !p32 && ((lpw == 8 && C == 25) || (lpw == 16 && C == 13));
-      const int slack = fixc ? std::max(SLACK, (lpw * C - window) * A + 4) : SLACK;
-      constexpr int NR = MLP ? reg_nrm_floats(A) : 0;
-      auto span_bytes = [&](int wpb) -> int64_t {
-        if (p32) return (NR + PAD + (int64_t)wpb * p32_pitch(window, A) + slack) * (int64_t)sizeof(float);
-        if (ipw) return (NR + PAD + (int64_t)wpb * ipw + slack) * (int64_t)sizeof(float);
-        return (NR + PAD + ((int64_t)(wpb - 1) * stride + window) * A + slack) * (int64_t)sizeof(float);
-      };
-      // waves per block: a multiple of T3, at most 4; the most whose span fits 48 KB (>= 3 blocks per CU)
-      int m = 0;
-      // (measured on the stride-100 shape: 2- and 1-wave blocks 70 / 68 us vs 64 us with 4 — the staged span is
-      // shared by fewer windows and more blocks start on a stage)
-      for (int mm = 4 / T3; mm >= 1; --mm)
-        if (span_bytes(mm * gpw) <= 48 * 1024) { m = mm; break; }
-      if (!m && span_bytes(gpw) <= 160 * 1024) m = 1;
-      if (m) {
-        const int wpb = m * gpw, nt = 64 * T3 * m;
-        const int64_t nblk = (n_windows + wpb - 1) / wpb;
-        const size_t bytes = (size_t)span_bytes(wpb);
-        const unsigned grid = (unsigned)nblk;  // one-shot blocks (a persistent DMA-prefetch variant measured slower)
+  // ---- the register-resident kernel: every shape whose staged span fits the LDS ----
+  // the smallest group (8 / 16 / 32 / 64 lanes), then the shortest odd run C <= 31 (lanes C*A
+  // floats apart hit distinct LDS banks for odd A) with LPW * C >= W (W <= 1984): the fewer lanes
+  // per window, the fewer cross-lane reductions per sample (~a third of the VALU at 32 lanes)
+  // (8-lane groups only for overlapping windows: their span is shared, so the LDS per window — which
+  // bounds the waves per CU — stays small; measured: W = 200 stride 100 69 vs 77 us, stride 200 54
+  // vs 47 us with 8- vs 16-lane groups; round 6 with fixed-length runs, stride 100: 64 vs 77.5 us)
+  int lpw = 0, C = 0;
+  for (int l = stride < window ? 8 : 16; l <= 64 && !lpw; l *= 2)
+    for (int c = 5; c <= RCMAX_LONG; c += 2)
+      if (l * c >= window) { lpw = l; C = c; break; }
+  // (Rejected, profiles/r4/lr_dense_mfma.md: 16-lane groups of 32-sample runs on per-window images padded
+  // every 32 samples for the 9-axis 500-sample shape instead of 32 x 17 — 364 vs 328 us: four windows'
+  // images per 3-wave block (73 KB) halve the resident waves, which costs more than the saved reductions.)
+  if (lpw) {
+    const int gpw = 64 / lpw;
+    // non-overlapping 16-lane windows: padded images, pitch = 16 (mod 32) floats (see the kernel)
+    const bool pimg = lpw == 16 && A % 2 == 1 && stride == window && (window * A) % 4 == 0 &&
+                      (reinterpret_cast<uintptr_t>(stream) & 15) == 0 && (window * A) % 32 != 16;
+    const int ipw = pimg ? window * A + (((16 - window * A) % 32) + 32) % 32 : 0;
+    // (the fixed-length runs read D = lpw C - window samples past the last window unclamped)
+    const bool fixc = (lpw == 8 && C == 25) || (lpw == 16 && C == 13);
+    const int slack = fixc ? std::max(SLACK, (lpw * C - window) * A + 4) : SLACK;
+    constexpr int NR = MLP ? reg_nrm_floats(A) : 0;
+    auto span_bytes = [&](int wpb) -> int64_t {
+      if (ipw) return (NR + PAD + (int64_t)wpb * ipw + slack) * (int64_t)sizeof(float);
+      return (NR + PAD + ((int64_t)(wpb - 1) * stride + window) * A + slack) * (int64_t)sizeof(float);
+    };
+    // waves per block: a multiple of T3, at most 4; the most whose span fits 48 KB (>= 3 blocks per CU)
+    int m = 0;
+    // (measured on the stride-100 shape: 2- and 1-wave blocks 70 / 68 us vs 64 us with 4 — the staged span is
+    // shared by fewer windows and more blocks start on a stage)
+    for (int mm = 4 / T3; mm >= 1; --mm)
+      if (span_bytes(mm * gpw) <= 48 * 1024) { m = mm; break; }
+    if (!m && span_bytes(gpw) <= 160 * 1024) m = 1;
+    if (m) {
+      const int wpb = m * gpw, nt = 64 * T3 * m;
+      const int64_t nblk = (n_windows + wpb - 1) / wpb;
+      const size_t bytes = (size_t)span_bytes(wpb);
+      const unsigned grid = (unsigned)nblk;  // one-shot blocks (a persistent DMA-prefetch variant measured slower)
 #define HAR_WIN_R(L)                                                                                          \
   if (C <= 17)                                                                                             \
     window_features_reg_kernel<A, L, MLP, 17><<<grid, nt, bytes, s>>>(stream, window, stride, n_windows, ms, out, \
@@ -1012,49 +843,65 @@ int launch_axes(const float* stream, int64_t n_samples, int window, int stride, 
   else                                                                                                     \
     window_features_reg_kernel<A, L, MLP, RCMAX_LONG><<<grid, nt, bytes, s>>>(stream, window, stride, n_windows, \
                                                                               ms, out, ld_out, mo, C, wpb, ipw)
-        if (p32)
-          window_features_reg_kernel<A, 16, MLP, 32, true><<<grid, nt, bytes, s>>>(stream, window, stride, n_windows,
-                                                                                   ms, out, ld_out, mo, C, wpb, ipw);
-        else if (lpw == 8 && C == 25) {  // (the stride-100 200-sample shape: 8 x 25, held to 128 VGPRs: 4 waves
-                                          // per SIMD, not 3; fixed-length runs)
-          window_features_reg_kernel<A, 8, MLP, 25, false, 4, true><<<grid, nt, bytes, s>>>(
-              stream, window, stride, n_windows, ms, out, ld_out, mo, C, wpb, ipw);
-        }
-        else if (lpw == 16 && C == 13)  // (the 200-sample non-overlapping shape: 16 x 13, fixed-length runs)
-          window_features_reg_kernel<A, 16, MLP, 13, false, 1, true><<<grid, nt, bytes, s>>>(
-              stream, window, stride, n_windows, ms, out, ld_out, mo, C, wpb, ipw);
-        else if (lpw == 8) { HAR_WIN_R(8); }
-        else if (lpw == 16) { HAR_WIN_R(16); }
-        else if (lpw == 32) { HAR_WIN_R(32); }
-        else { HAR_WIN_R(64); }
-#undef HAR_WIN_R
-        HAR_CHECK_LAUNCH();
-        return 0;
+      if (lpw == 8 && C == 25) {  // (the stride-100 200-sample shape: 8 x 25, held to 128 VGPRs: 4 waves
+                                   // per SIMD, not 3; fixed-length runs)
+        window_features_reg_kernel<A, 8, MLP, 25, 4, true><<<grid, nt, bytes, s>>>(
+            stream, window, stride, n_windows, ms, out, ld_out, mo, C, wpb, ipw);
       }
+      else if (lpw == 16 && C == 13)  // (the 200-sample non-overlapping shape: 16 x 13, fixed-length runs)
+        window_features_reg_kernel<A, 16, MLP, 13, 1, true><<<grid, nt, bytes, s>>>(
+            stream, window, stride, n_windows, ms, out, ld_out, mo, C, wpb, ipw);
+      else if (lpw == 8) { HAR_WIN_R(8); }
+      else if (lpw == 16) { HAR_WIN_R(16); }
+      else if (lpw == 32) { HAR_WIN_R(32); }
+      else { HAR_WIN_R(64); }
+#undef HAR_WIN_R
+      HAR_CHECK_LAUNCH();
+      return 0;
     }
   }
-  // 8-lane groups (half the reduction and write-out work per window) when two waves' sixteen
-  // 3-axis windows fit 64 KB — the short-window WISDM case; else 16-lane groups
-  if constexpr (A == 3) {
-    if (lds_bytes(16, pitch_for(8)) <= 64 * 1024) return launch(std::integral_constant<int, 8>{}, 2, pitch_for(8));
+  // ---- the fallback kernel: long windows (window > 1984) and sparse strides (the span above exceeds the
+  // LDS), one image per window ----
+  // image pitch: 16 A (mod 64) dwords for odd A (conflict-free rows, see the kernel); 32 (mod 64)
+  // for A = 6 (even A only ever reaches even banks: rows one image apart stay disjoint)
+  const int n = window * A;
+  // do the 64 lanes of a wave (rows one image apart, lanes A floats apart) hit 64 distinct banks?
+  auto conflict_free = [&](int pitch) {
+    uint64_t seen = 0;
+    for (int l = 0; l < 64; ++l) {
+      const uint64_t bit = 1ull << (((l / FLPW) * pitch + (l % FLPW) * A) & 63);
+      if (seen & bit) return false;
+      seen |= bit;
+    }
+    return true;
+  };
+  // (non-overlapping windows: contiguous images unless that costs bank conflicts)
+  int pitch = n;
+  if (!(stride == window && n % 4 == 0 && (conflict_free(n) || A % 2 == 0))) {
+    const int want = (A % 2) ? (FLPW * A) % 64 : 32;
+    pitch = n + (((want - n) % 64) + 64) % 64;
   }
-  const int pitch = pitch_for(16);
+  auto lds_bytes = [&](int wpb) -> int64_t {
+    return (PAD + (int64_t)wpb * pitch + SLACK) * (int64_t)sizeof(float);
+  };
   // waves per block: a multiple of T3 (whole windows); the most whose images fit 64 KB (three or
   // more blocks per CU), else the fewest if they fit the 160 KB LDS
   int waves = 0;
   for (int w = 4; w >= 1; --w) {
     if (w % T3) continue;
-    if (lds_bytes(4 * w / T3, pitch) <= 64 * 1024) { waves = w; break; }
+    if (lds_bytes(4 * w / T3) <= 64 * 1024) { waves = w; break; }
   }
-  if (!waves && lds_bytes(4, pitch) <= 160 * 1024) waves = T3;
+  if (!waves && lds_bytes(4) <= 160 * 1024) waves = T3;
   if (!waves) return -5;  // one block's windows do not fit the LDS
-  return launch(std::integral_constant<int, 16>{}, waves, pitch);
+  const int wpb = 4 * waves / T3;
+  window_features_fallback_kernel<A, MLP><<<(unsigned)((n_windows + wpb - 1) / wpb), 64 * waves,
+                                            (size_t)lds_bytes(wpb), s>>>(stream, n_samples, window, stride, n_windows,
+                                                                         ms, out, ld_out, mo, pitch);
+  HAR_CHECK_LAUNCH();
+  return 0;
 }
 
-
 }  // namespace
-
-extern "C" void har_window_set_legacy(int on) { g_window_legacy = on != 0; }
 
 extern "C" int har_window_features(const float* stream, int64_t n_samples, int axes, int window, int stride,
                                    int64_t n_windows, float hz, int nbins, float* out, int ld_out, hipStream_t s) {

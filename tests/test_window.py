@@ -235,3 +235,49 @@ def test_window_kernel_long_windows_match_torch(cuda, axes, window, stride):
     assert mo.shape == (ref.shape[0], (F + 31) // 32 * 32) and torch.count_nonzero(mo[:, F:]) == 0
     want = torch.nan_to_num(out, nan=-1.0).to(torch.bfloat16)
     torch.testing.assert_close(mo[:, :F].float().cpu(), want.float(), rtol=2 ** -7, atol=1e-3)
+
+
+# (axes, window, stride, windows): the window counts give a full block and a ragged last one (nwin < wpb)
+# of the kernel each shape takes — 16 / 8 / 4 windows per fallback block for 3 / 6 / 9 axes, 4 per
+# register-kernel block at these strides
+_SPARSE_SHAPES = [(3, 200, 5000, 19), (3, 200, 4400, 19), (6, 200, 3000, 11), (9, 33, 2000, 10), (3, 64, 5003, 19)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("axes,window,stride,nwin", _SPARSE_SHAPES)
+def test_window_kernel_sparse_strides_match_torch(cuda, axes, window, stride, nwin):
+    """Sparse strides: stride so much larger than the window that the contiguous span of one wave's four
+    windows, ``(3 stride + window) axes`` floats plus the pads, no longer fits the 160 KB (40,960-float) LDS,
+    so the launcher leaves the register-resident kernel for the one-image-per-window fallback kernel.
+    From the launcher's ``span_bytes`` (pads: 12 + 28 floats at 3 axes x 200, 12 + 52 at 6 x 200, 12 + 16 for
+    the short windows; MLP rows add the 112 / 220 / 332-float normalization image):
+
+    * (3, 200, 5000): 40 + 9 x 5000 + 600 = 45,640 floats — fallback, fp32 and MLP rows (the boundary is
+      stride 4480 for fp32 rows, 4467 for MLP rows);
+    * (3, 200, 4400): 40,240 floats (40,352 for MLP rows) — still the register kernel's 16 x 13 shape;
+    * (6, 200, 3000): 64 + 6 x 9200 = 55,264 floats — fallback, two triads per window;
+    * (9, 33, 2000): 28 + 9 x 6033 = 54,325 floats — fallback, three triads per window, 3-iteration lanes;
+    * (3, 64, 5003): 28 + 3 x 15,073 = 45,247 floats — fallback; ``stride * axes`` = 15,009 is no multiple
+      of 4, so the windows do not start on a float4 and the kernel stages them with its scalar loop.
+
+    All against the PyTorch oracle on the CPU: fp32 features, then the MLP-input rows."""
+    from har.features.window import window_features, window_features_mlp
+
+    n_samples = (nwin - 1) * stride + window
+    spec = StreamSpec(axes=axes, window=max(window, 16), seed=window + axes)
+    s, _ = generate_stream((n_samples + spec.window - 1) // spec.window, spec)
+    s = s[:n_samples]
+    assert window_count(s.shape[0], window, stride) == nwin
+    ref = window_features_torch(s, window, stride, 50.0)
+    out = window_features(s.to(cuda), window, stride, 50.0).cpu()
+    assert out.shape == ref.shape == (nwin, n_features(axes))
+    nb = 10 * axes
+    assert (out[:, :nb] - ref[:, :nb]).abs().max() <= 1.0 / window + 1e-6
+    torch.testing.assert_close(out[:, nb:], ref[:, nb:], rtol=2e-4, atol=2e-4, equal_nan=True)
+    F = n_features(axes)
+    pad = (F + 31) // 32 * 32
+    mo = window_features_mlp(s.to(cuda), window, stride, 50.0, torch.zeros(F, device=cuda),
+                             torch.ones(F, device=cuda), pad)
+    assert mo.shape == (nwin, pad) and torch.count_nonzero(mo[:, F:]) == 0
+    want = torch.nan_to_num(out, nan=-1.0).to(torch.bfloat16)
+    torch.testing.assert_close(mo[:, :F].float().cpu(), want.float(), rtol=2 ** -7, atol=1e-3)

@@ -32,11 +32,6 @@ while time.time() - t0 < 0.5:
         a @ a
     torch.cuda.synchronize()
 
-from har.ops import _native  # noqa: E402
-
-mod = _native.kernels()
-
-
 def timed(fn, reps=20):
     """us per launch (HIP events around `reps` back-to-back launches, best of 3)"""
     fn()
@@ -53,21 +48,18 @@ def timed(fn, reps=20):
     return best
 
 
-modes = [("v3", 0), ("legacy", 1)] if os.environ.get("HAR_WINDOW_AB", "1") != "0" else [("v3", 0)]
-for name, legacy in modes:
-    mod.window_set_legacy(legacy)
-    for s, W, hz in streams:
-        us = timed(lambda: window_features(s, W, W, hz))
-        gb = s.numel() * 4 / 1e9
-        print(f"{name:7s} {s.shape[1]} axes W={W} stride={W}: {us:8.1f} us  {gb / us * 1e3:6.2f} TB/s ({gb:.3f} GB)")
-    us = timed(lambda: window_features_mlp(s3, 200, 200, 20.0, mean, inv, 64, -1.0, out=out))
-    print(f"{name:7s} 3 axes W=200 MLP rows : {us:8.1f} us  {s3.numel() * 4 / us / 1e6:6.2f} TB/s")
-    us = timed(lambda: window_features(s3, 200, 100, 20.0))
-    print(f"{name:7s} 3 axes W=200 stride=100: {us:8.1f} us  {s3.numel() * 4 / us / 1e6:6.2f} TB/s ({s3.shape[0] // 100 - 1} windows)")
-    # the 1B-sample stream pass's kernel: 50%-overlapping windows straight into bf16 MLP rows
-    out2 = torch.empty(s3.shape[0] // 100 - 1, 64, dtype=torch.bfloat16, device=dev)
-    us = timed(lambda: window_features_mlp(s3, 200, 100, 20.0, mean, inv, 64, -1.0, out=out2))
-    print(f"{name:7s} 3 axes W=200 stride=100 MLP rows: {us:8.1f} us  ({out2.shape[0] / us * 1e-3:.2f} G windows/s)")
-mod.window_set_legacy(0)
+name = "v3"  # (the row label of profiles/r3 .. r6: the register-resident kernel)
+for s, W, hz in streams:
+    us = timed(lambda: window_features(s, W, W, hz))
+    gb = s.numel() * 4 / 1e9
+    print(f"{name:7s} {s.shape[1]} axes W={W} stride={W}: {us:8.1f} us  {gb / us * 1e3:6.2f} TB/s ({gb:.3f} GB)")
+us = timed(lambda: window_features_mlp(s3, 200, 200, 20.0, mean, inv, 64, -1.0, out=out))
+print(f"{name:7s} 3 axes W=200 MLP rows : {us:8.1f} us  {s3.numel() * 4 / us / 1e6:6.2f} TB/s")
+us = timed(lambda: window_features(s3, 200, 100, 20.0))
+print(f"{name:7s} 3 axes W=200 stride=100: {us:8.1f} us  {s3.numel() * 4 / us / 1e6:6.2f} TB/s ({s3.shape[0] // 100 - 1} windows)")
+# the 1B-sample stream pass's kernel: 50%-overlapping windows straight into bf16 MLP rows
+out2 = torch.empty(s3.shape[0] // 100 - 1, 64, dtype=torch.bfloat16, device=dev)
+us = timed(lambda: window_features_mlp(s3, 200, 100, 20.0, mean, inv, 64, -1.0, out=out2))
+print(f"{name:7s} 3 axes W=200 stride=100 MLP rows: {us:8.1f} us  ({out2.shape[0] / us * 1e-3:.2f} G windows/s)")
 torch.cuda.synchronize()
 print("ok")
