@@ -243,11 +243,13 @@ __global__ void cast_pad_kernel(const float* __restrict__ in, int rows, int cin,
 //   GR_REFRESH (alone) the bf16 copy and the fragment copies from param, no update: the sharded DP
 //              step after its all-gather of the fp32 parameters (one launch instead of a torch cast +
 //              the pack kernel)
-// A workgroup = GR_W (4 by default; 8 / 16 by HAR_GR_W) waves x 64 float4 columns: wave q sums slabs
-// q, q + GR_W, q + 2 GR_W, ... (eight loads in flight per step), the GR_W partials are added in a
-// fixed tree order -> bitwise reproducible, and N = 1 (GR_REDUCE |
-// GR_ADAM) and N > 1 (GR_REDUCE | GR_STORE, all-reduce, GR_ADAM) apply the same summation and the
-// same Adam arithmetic.  With fragment copies (MlpFragSpec) the new bf16 values also go to the W0 and
+// A workgroup = GR_W = 4 waves x 64 float4 columns: wave q sums slabs q, q + 4, q + 8, ... (eight
+// loads in flight per step), the 4 partials are added in a fixed tree order -> bitwise reproducible,
+// and N = 1 (GR_REDUCE | GR_ADAM) and N > 1 (GR_REDUCE | GR_STORE, all-reduce, GR_ADAM) apply the same
+// summation and the same Adam arithmetic.  (8 and 16 waves per workgroup, and 16 loads in flight at
+// 4 waves, were tried and lost: flagship reduction + Adam 4.9 us at 4 waves, 5.4 at 8, 6.6 at 16, 5.3
+// with 16 loads in flight, profiles/r4/qn_workgroups_grw.md.)
+// With fragment copies (MlpFragSpec) the new bf16 values also go to the W0 and
 // W1 fragment copies (8-byte runs); the W1^T copy is written by the step's forward kernel, which
 // holds W1 in registers anyway (a tiled transposing variant of this kernel measured 1.5 us slower).
 // Prefetch workgroups (PrefetchSpec: blocks main_blocks .. of the launch): the NEXT step's input rows read
@@ -259,8 +261,8 @@ __global__ void cast_pad_kernel(const float* __restrict__ in, int rows, int cin,
 // so every thread's loads stay.
 struct PrefetchSpec {
   const uint32_t* p;   // region 0 (the rows) ...
-  int64_t lines;       // ... in lines of `dw` dwords (64 bytes; HAR_PF_LINE)
-  int dw;
+  int64_t lines;       // ... in lines of `dw` dwords
+  int dw;              // 16: one touch per 64 bytes (128 / 256 bytes: worse than no prefetch, same file)
   const uint32_t* p1;  // region 1 (the labels), its lines follow region 0's
   int64_t lines1;
   uint32_t* sink;
@@ -268,13 +270,13 @@ struct PrefetchSpec {
 };
 
 constexpr int GR_REDUCE = 1, GR_STORE = 2, GR_ADAM = 4, GR_REFRESH = 8;
-template <int GR_W>  // waves per workgroup
+constexpr int GR_W = 4;  // waves per workgroup
 __global__ __launch_bounds__(64 * GR_W) void grad_reduce_adam_kernel(GradRegions rg, int64_t n, float* __restrict__ G,
                                                                 float* __restrict__ param, float* __restrict__ m,
                                                                 float* __restrict__ v, bf16_t* __restrict__ pb,
                                                                 float lr, float b1, float b2, float eps, float wd,
                                                                 const int32_t* __restrict__ step, int mode,
-                                                                MlpFragSpec frag, int wide, PrefetchSpec pf) {
+                                                                MlpFragSpec frag, PrefetchSpec pf) {
   if ((int)blockIdx.x >= pf.main_blocks) {  // a prefetch workgroup (uniform per block)
     const int64_t nt = (int64_t)(gridDim.x - pf.main_blocks) * blockDim.x;
     const int64_t t0 = (int64_t)(blockIdx.x - pf.main_blocks) * blockDim.x + threadIdx.x;
@@ -328,21 +330,6 @@ __global__ __launch_bounds__(64 * GR_W) void grad_reduce_adam_kernel(GradRegions
         const int S = rg.S[r];
         const int64_t ld = rg.lds[r];
         int s = q;
-        if (wide) {  // 16 loads in flight per step (HAR_GR_NL=16)
-          for (; s + 15 * GR_W < S; s += 16 * GR_W) {
-            float4 x[16];
-#pragma unroll
-            for (int j = 0; j < 16; ++j) x[j] = *reinterpret_cast<const float4*>(p + (size_t)(s + j * GR_W) * ld);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-              x[j].x += x[j + 8].x; x[j].y += x[j + 8].y; x[j].z += x[j + 8].z; x[j].w += x[j + 8].w;
-            }
-            acc.x += ((x[0].x + x[1].x) + (x[2].x + x[3].x)) + ((x[4].x + x[5].x) + (x[6].x + x[7].x));
-            acc.y += ((x[0].y + x[1].y) + (x[2].y + x[3].y)) + ((x[4].y + x[5].y) + (x[6].y + x[7].y));
-            acc.z += ((x[0].z + x[1].z) + (x[2].z + x[3].z)) + ((x[4].z + x[5].z) + (x[6].z + x[7].z));
-            acc.w += ((x[0].w + x[1].w) + (x[2].w + x[3].w)) + ((x[4].w + x[5].w) + (x[6].w + x[7].w));
-          }
-        }
         for (; s + 7 * GR_W < S; s += 8 * GR_W) {
           float4 x[8];
 #pragma unroll
@@ -369,16 +356,6 @@ __global__ __launch_bounds__(64 * GR_W) void grad_reduce_adam_kernel(GradRegions
     }
     part[q][k] = acc;
     __syncthreads();
-    if (GR_W == 16 && q < 4) {  // 16 -> 4 partials (fixed pairs)
-      const float4 a = part[q][k], b = part[q + 4][k], c = part[q + 8][k], d = part[q + 12][k];
-      part[q][k] = make_float4((a.x + b.x) + (c.x + d.x), (a.y + b.y) + (c.y + d.y), (a.z + b.z) + (c.z + d.z),
-                               (a.w + b.w) + (c.w + d.w));
-    }
-    if (GR_W == 8 && q < 4) {
-      const float4 a = part[q][k], b = part[q + 4][k];
-      part[q][k] = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
-    }
-    if (GR_W > 4) __syncthreads();
   }
   if (q == 0 && e < n) {
     float4 g;
@@ -501,35 +478,14 @@ extern "C" int har_grad_reduce_adam(int nreg, const float* const* src, const int
   if (blocks == 0) return 0;
   if (tick) adam_tick_kernel<<<1, 1, 0, s>>>(step);
   // prefetch workgroups: one per 2048 lines (8 loads per thread), at most 256
-  static const int pf_line = [] {  // bytes per touched line (tuning: HAR_PF_LINE = 64 / 128 / 256)
-    const char* e = getenv("HAR_PF_LINE");
-    const int v = e ? atoi(e) : 64;
-    return v == 128 || v == 256 ? v : 64;
-  }();
+  constexpr int pf_line = 64;  // bytes per touched line
   PrefetchSpec ps{reinterpret_cast<const uint32_t*>(pf), pf ? pf_bytes / pf_line : 0, pf_line / 4,
                   reinterpret_cast<const uint32_t*>(pf1), pf && pf1 ? pf1_bytes / pf_line : 0, pf_sink, (int)blocks};
   const int64_t pfl = ps.lines + ps.lines1;
   const int64_t pfb = pf && pfl > 0 ? std::min<int64_t>(256, (pfl + 2047) / 2048) : 0;
   const int64_t grid = blocks + pfb;
-  // waves per workgroup: 4 (tools/gpu_qnwg_ab.sh a: flagship reduction + Adam 6.6 -> 4.9 us with 64 slabs,
-  // the small-batch step 21.7 -> 20.8 us with 8; 8 waves 5.4 / 20.9; 16 was the round-3 choice)
-  static const int w = [] {
-    const char* e = getenv("HAR_GR_W");
-    return e ? atoi(e) : 4;
-  }();
-  static const int wide = [] {
-    const char* e = getenv("HAR_GR_NL");
-    return e && atoi(e) == 16 ? 1 : 0;
-  }();
-  if (w == 4)
-    grad_reduce_adam_kernel<4><<<(int)grid, 256, 0, s>>>(rg, n, G, param, m, v, pb, lr, b1, b2, eps, wd, step, mode,
-                                                         frag, wide, ps);
-  else if (w == 8)
-    grad_reduce_adam_kernel<8><<<(int)grid, 512, 0, s>>>(rg, n, G, param, m, v, pb, lr, b1, b2, eps, wd, step, mode,
-                                                         frag, wide, ps);
-  else
-    grad_reduce_adam_kernel<16><<<(int)grid, 1024, 0, s>>>(rg, n, G, param, m, v, pb, lr, b1, b2, eps, wd, step,
-                                                           mode, frag, wide, ps);
+  grad_reduce_adam_kernel<<<(int)grid, 64 * GR_W, 0, s>>>(rg, n, G, param, m, v, pb, lr, b1, b2, eps, wd, step, mode,
+                                                          frag, ps);
   HAR_CHECK_LAUNCH();
   return 0;
 }

@@ -30,7 +30,6 @@
 // One deterministic partial per (slice, quadrant), laid out like the flat parameter buffer.
 #include <algorithm>
 #include <type_traits>
-#include <cstdlib>
 
 #include "common.h"
 #include "mlp_frag.h"
@@ -81,19 +80,7 @@ constexpr int FIMG = FRT * FSP;
 // softmax lanes (row, class) then read 16 distinct banks per row and disjoint banks per row pair
 constexpr int ZREG = 4 * 72;
 constexpr int FWD_SLAB = NCLS * HH + NCLS;  // per workgroup: dWout rows 0..15 [16][H], dbout [16]
-#ifndef HAR_FWD_PD
-#define HAR_FWD_PD 2
-#endif
-#ifndef HAR_FWD_KROT
-#define HAR_FWD_KROT 0
-#endif
-#ifndef HAR_FWD_PIN
-#define HAR_FWD_PIN 1
-#endif
-constexpr int FPD = HAR_FWD_PD;      // stage-2 h1 read prefetch distance (k chunks)
-constexpr bool FPIN = HAR_FWD_PIN;   // pin the read / MFMA interleave with scheduling groups
-// FILL (template argument, HAR_MLP_FWD_FILL): VALU instructions of the tile's softmax interleaved
-// after each stage-2 MFMA (0: the softmax runs on its own, before stage 5)
+constexpr int FPD = 2;  // stage-2 h1 read prefetch distance (k chunks)
 constexpr size_t FWD_LDS = (size_t)2 * FRT * FHP * 2 + (size_t)2 * FW * 2 * ZREG * 4 + (size_t)2 * FIMG * 2 +
                            (size_t)FW * 4 * FIMG * 2;
 
@@ -104,14 +91,14 @@ __device__ __forceinline__ bf16x8_t ldx(const bf16_t* __restrict__ X, int row, i
 
 // INFER: the serving forward of the same pipeline — no labels, no dz / relu' mask / dWout / W1^T copy;
 // `slab` receives the logits [B][C] (fp32, bias included) and `block_correct` the argmax [B].
-template <int K0, bool STAMP, bool INFER = false, int FFILL = 0>
+template <int K0, bool STAMP, bool INFER = false>
 __global__ __launch_bounds__(512) void mlp_fwd3_kernel(
     const bf16_t* __restrict__ X, bf16_t* __restrict__ Wf, const float* __restrict__ b0,
     const float* __restrict__ b1, const bf16_t* __restrict__ Wo,
     const float* __restrict__ bo, const int32_t* __restrict__ labels, int B, int C, float scale,
     bf16_t* __restrict__ dact2_out, float* __restrict__ slab,
     float* __restrict__ block_loss, int32_t* __restrict__ block_correct, uint64_t* __restrict__ stamps,
-    int stagger, int wt) {
+    int wt) {
   constexpr int K0C = K0 / 32, KC = HH / 32;
   extern __shared__ __attribute__((aligned(16))) bf16_t lds[];
   bf16_t* const h1s = lds;                                                // [2 bufs][32][FHP]
@@ -153,11 +140,6 @@ __global__ __launch_bounds__(512) void mlp_fwd3_kernel(
   const bf16_t* const W0f = Wf;
   const bf16_t* const W1f = Wf + HH * K0;
   bf16x8_t w0f[2][K0C], w1f[2][KC];
-  // k-chunk rotation per workgroup (register kc holds chunk (kc + krot)): the CUs' prologue requests
-  // spread over the lines of W1 instead of all asking for the same ones together
-  // (off: with a per-workgroup rotation every stage-2 LDS read needs a VALU address add; the rotation
-  // did not measurably shorten the prologue)
-  const int krot = HAR_FWD_KROT ? (int)blockIdx.x & (KC - 1) : 0;
   float4 b0r[2], b1r[2];
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
@@ -174,13 +156,15 @@ __global__ __launch_bounds__(512) void mlp_fwd3_kernel(
   __builtin_amdgcn_sched_barrier(0);
   // b1 first, then W1 k-chunk-major (both unit tiles of chunk kc together): tile 0's stage 2 waits, at
   // chunk kc, only for the loads up to that chunk, so the tail of the W1 stream overlaps its MFMAs
+  // (rotating the chunk order per workgroup, so that the CUs' prologue requests spread over the lines
+  // of W1, did not measurably shorten the prologue and cost every stage-2 LDS read a VALU address add)
 #pragma unroll
   for (int t = 0; t < 2; ++t) b1r[t] = *reinterpret_cast<const float4*>(b1 + u0 + 16 * t + 4 * g);
 #pragma unroll
   for (int kc = 0; kc < KC; ++kc)
 #pragma unroll
     for (int t = 0; t < 2; ++t)
-      w1f[t][kc] = *reinterpret_cast<const bf16x8_t*>(W1f + (size_t)((2 * wave + t) * KC + ((kc + krot) & (KC - 1))) * 512 + frag_lane_off(lane));
+      w1f[t][kc] = *reinterpret_cast<const bf16x8_t*>(W1f + (size_t)((2 * wave + t) * KC + kc) * 512 + frag_lane_off(lane));
   // stage-3 A fragment: Wout[class c16][u0 + 4g + j] (j < 4), [u0 + 16 + 4g + j - 4] (j >= 4): the k
   // order of the h2 register pairs (C layout: unit 4g + r of a 16-unit tile in register r)
   const uint2 wlo = *reinterpret_cast<const uint2*>(Wo + (size_t)c16 * HH + u0 + 4 * g);
@@ -222,7 +206,7 @@ __global__ __launch_bounds__(512) void mlp_fwd3_kernel(
   };
   // ---- stages 2 + 3 of tile k from h1 buffer `buf`: h2^T = W1 . h1^T, relu' mask, partial logits
   // -> zs buffer `buf`, h2 images for stage 5 -> image buffer `buf` ----
-  auto stage23 = [&](int k, int buf, auto&& fill) __attribute__((always_inline)) {
+  auto stage23 = [&](int k, int buf) __attribute__((always_inline)) {
     const int r0 = tile_of(k) * FRT;
     const bf16_t* hsrc = h1s + buf * FRT * FHP;
     f32x4_t acc[2][2];
@@ -234,43 +218,32 @@ __global__ __launch_bounds__(512) void mlp_fwd3_kernel(
     // reads of chunk kc + FPD, then the 4 MFMAs of chunk kc).  Left to the scheduler each chunk's two
     // reads were issued right before its MFMAs and every chunk waited out an LDS round trip (stage
     // 2 + 3 ~1.9k cycles per wave for 34 MFMAs, profiles/r5)
+    // (Filling the MFMA shadow with the previous tile's softmax, one or two of its VALU instructions
+    // pinned after each of these MFMAs, was tried and lost: step 0.0611 - 0.0625 against 0.0602 -
+    // 0.0606 ms, profiles/r5/mlp_ab_same_box.md.)
     bf16x8_t hb[KC][2];
-    if constexpr (FPIN) __builtin_amdgcn_sched_barrier(0);  // an isolated region: the groups take only these
+    __builtin_amdgcn_sched_barrier(0);  // an isolated region: the groups take only these
     auto ld_hb = [&](int kc) __attribute__((always_inline)) {
 #pragma unroll
       for (int h = 0; h < 2; ++h)
-        hb[kc][h] = *reinterpret_cast<const bf16x8_t*>(hsrc + (16 * h + c16) * FHP +
-                                                        ((8 * g) ^ hsw) + ((kc + krot) & (KC - 1)) * 32);
+        hb[kc][h] = *reinterpret_cast<const bf16x8_t*>(hsrc + (16 * h + c16) * FHP + ((8 * g) ^ hsw) + kc * 32);
     };
 #pragma unroll
     for (int kc = 0; kc < FPD; ++kc) ld_hb(kc);
-    // the previous tile's softmax (a dependent VALU / DPP chain on partial logits read before stage 5):
-    // its VALU work goes into the MFMA shadow, FFILL instructions after each MFMA
-    fill();
-    if constexpr (FPIN) __builtin_amdgcn_sched_group_barrier(0x100, 2 * FPD, 0);  // the FPD chunks ahead
+    __builtin_amdgcn_sched_group_barrier(0x100, 2 * FPD, 0);  // the FPD chunks ahead
 #pragma unroll
     for (int kc = 0; kc < KC; ++kc) {
       if (kc + FPD < KC) {
         ld_hb(kc + FPD);
-        if constexpr (FPIN) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
       }
 #pragma unroll
       for (int h = 0; h < 2; ++h)
 #pragma unroll
         for (int t = 0; t < 2; ++t) acc[h][t] = mma32(w1f[t][kc], hb[kc][h], acc[h][t]);
-      if constexpr (FPIN) {
-        if constexpr (FFILL > 0) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x002, FFILL, 0);
-          }
-        } else {
-          __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-        }
-      }
+      __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
     }
-    if constexpr (FPIN) __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_sched_barrier(0);
     uint32_t h2p[2][2][2];
 #pragma unroll
     for (int h = 0; h < 2; ++h)
@@ -297,13 +270,11 @@ __global__ __launch_bounds__(512) void mlp_fwd3_kernel(
     }
   };
   // ---- softmax / CE / argmax / dz of tile k (zs buffer `buf`): lane = (row sr, class c16) ----
-  // (split: sm_load issues the 8 partial-logit reads, sm_compute the rest)
-  auto sm_load = [&](int buf, float (&zp)[FW]) __attribute__((always_inline)) {
+  auto softmax = [&](int k, int buf, int yc) __attribute__((always_inline)) {
     const float* zb = zs + buf * FW * 2 * ZREG;
+    float zp[FW];
 #pragma unroll
     for (int w = 0; w < FW; ++w) zp[w] = zb[(w * 2 + sh) * ZREG + 72 * (c16 >> 2) + 4 * srr + (c16 & 3)];
-  };
-  auto sm_compute = [&](int k, int buf, int yc, const float (&zp)[FW]) __attribute__((always_inline)) {
     const int r0 = tile_of(k) * FRT;
     float z = 0.f;
 #pragma unroll
@@ -330,12 +301,6 @@ __global__ __launch_bounds__(512) void mlp_fwd3_kernel(
     dbo += bf2f(db);
     dzs[buf * FIMG + sr * FSP + (c16 ^ (8 * ((sr >> 3) & 1)))] = db;
   };
-  auto softmax = [&](int k, int buf, int yc) __attribute__((always_inline)) {
-    float zp[FW];
-    sm_load(buf, zp);
-    sm_compute(k, buf, yc, zp);
-  };
-  auto no_fill = [] {};
   // ---- stage 5 of a tile (dz buffer / image buffer `buf`, rows r0 ..): dWout^T += h2^T . dz over its
   // 32 rows, and the backward's layer-2 gradient dact2 = (dz . Wout) * relu'(h2) of the wave's 32
   // units -> dact2_out (bf16 [B][256], the 16-byte chunks of rows with bit 2 set swapped in pairs —
@@ -391,7 +356,7 @@ __global__ __launch_bounds__(512) void mlp_fwd3_kernel(
     stage1(0);
     load_x(1);
     __syncthreads();  // h1 of tile 0
-    stage23(0, 0, no_fill);
+    stage23(0, 0);
     stage1(1);
     load_x(2);
     __syncthreads();  // partial logits of tile 0, h1 of tile 1
@@ -400,37 +365,20 @@ __global__ __launch_bounds__(512) void mlp_fwd3_kernel(
   // iterations are peeled so the steady-state body is ONE basic block (no k > 0 / k + 1 < nt
   // branches): the scheduler can then interleave the softmax's VALU / DPP chain with the stage-2
   // MFMAs instead of running them back to back.
-  // Staggered roles (stagger != 0): the two waves of a SIMD (w and w + 4) run the SAME phases of an
-  // iteration in a different ORDER — waves 0..3 softmax(k) first, waves 4..7 last (after stage 5 and
-  // the next tile's MFMA stages) — so one wave's VALU / DPP softmax chain issues beside its partner's
-  // stage-2 MFMAs instead of both SIMD partners reaching the softmax (MFMA pipe idle) and then the
-  // MFMAs (pipe shared) together.  Legal: within an iteration the phases touch disjoint buffers
-  // (softmax: zs[k], dzs[k]; stage 5: dzs[k-1], the wave's own img[k-1]; stages 2 + 3: h1[k+1] ->
-  // zs[k+1], own img[k+1]; stage 1: h1[k+2]) and the wave's own img[k-1] is read before its img[k+1]
-  // (the same buffer) is written in both orders.
-  auto iter = [&](int k, bool first, bool last, auto late) __attribute__((always_inline)) {
+  // (Staggered roles — waves 4..7 of the workgroup running their softmax after stage 5 or last, so that
+  // one wave's VALU / DPP chain issues beside its SIMD partner's stage-2 MFMAs — were tried and lost:
+  // step medians 0.0585 / 0.0587 against 0.0582 ms, profiles/r5/mlp_ab_same_box.md; within box noise
+  // again in profiles/r6/mlp_knobs_resweep.txt.)
+  auto iter = [&](int k, bool first, bool last) __attribute__((always_inline)) {
     if (k < 32) HAR_STAMP(FW, 2 + k)
     const int yc = ynext;
     if constexpr (!INFER) ynext = (labels + (size_t)tile_of(k + 1) * FRT)[sr];
-    // softmax(k) inside the stage-2 region of tile k+1 (FFILL > 0; not in the stamped build, whose
-    // stamps would split it) or on its own
-    constexpr int SMP = decltype(late)::value;  // where the softmax runs: 0 first, 1 after stage 5, 2 last
-    constexpr bool fill = FFILL > 0 && !STAMP && SMP == 0;
-    float zp[FW];
-    if (fill && !last) {
-      sm_load(k & 1, zp);
-    } else if constexpr (SMP == 0) {
-      softmax(k, k & 1, yc);
-    }
+    softmax(k, k & 1, yc);
     if (k == 4) HAR_STAMP(FW, 10)
     if (!INFER && !first) stage5((k - 1) & 1, tile_of(k - 1) * FRT);
-    if constexpr (SMP == 1) softmax(k, k & 1, yc);
     if (k == 4) HAR_STAMP(FW, 11)
     if (!last) {
-      if (fill)
-        stage23(k + 1, (k + 1) & 1, [&] { sm_compute(k, k & 1, yc, zp); });
-      else
-        stage23(k + 1, (k + 1) & 1, no_fill);
+      stage23(k + 1, (k + 1) & 1);
       if (k == 4) HAR_STAMP(FW, 12)
       // stage 1 reads the X tile whose loads were issued just before the last barrier: hoisted to the
       // top of the body (as the scheduler likes, to fill the MFMA pipe beside the softmax) it waits out
@@ -442,30 +390,16 @@ __global__ __launch_bounds__(512) void mlp_fwd3_kernel(
       load_x(k + 3);
       if (k == 4) HAR_STAMP(FW, 13)
     }
-    if constexpr (SMP == 2) softmax(k, k & 1, yc);
     __syncthreads();
   };
   // (nt == 1 apart, so that every path into the loop issues its loads in the loop body's order: a
   // path with other pending loads makes the counted wait for the label at the loop top conservative)
-  auto run = [&](auto late) __attribute__((always_inline)) {
-    if (nt == 1) {
-      iter(0, true, true, late);
-    } else if (nt > 1) {
-      iter(0, true, false, late);
-      for (int k = 1; k < nt - 1; ++k) iter(k, false, false, late);
-      iter(nt - 1, false, true, late);
-    }
-  };
-  // stagger 1: waves 4..7 run their softmax last; 2: right after stage 5 (while waves 0..3, which ran
-  // theirs first, are in stage 5: the DPP / transcendental chain of one SIMD partner beside the LDS
-  // reads and MFMAs of the other, in both halves)
-  if (stagger && __builtin_amdgcn_readfirstlane(wave) >= FW / 2) {
-    if (stagger == 2)
-      run(std::integral_constant<int, 1>{});
-    else
-      run(std::integral_constant<int, 2>{});
-  } else {
-    run(std::integral_constant<int, 0>{});
+  if (nt == 1) {
+    iter(0, true, true);
+  } else if (nt > 1) {
+    iter(0, true, false);
+    for (int k = 1; k < nt - 1; ++k) iter(k, false, false);
+    iter(nt - 1, false, true);
   }
   HAR_STAMP(FW, 34)
   if constexpr (INFER) return;
@@ -478,7 +412,7 @@ __global__ __launch_bounds__(512) void mlp_fwd3_kernel(
     const int ub = f & 15, jc = f >> 4;
     if (wave == jc) {
       bf16_t* tt = h1s + wave * 32 * 24;  // this wave's [32 j][16 u] (+ pad)
-      const int kcs = ((ub >> 1) - krot) & (KC - 1);
+      const int kcs = ub >> 1;
 #pragma unroll
       for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -605,7 +539,7 @@ __global__ __launch_bounds__(512) void mlp_bwd4_kernel(
     int B, int S, float* __restrict__ gw1, float* __restrict__ gw0,
     float* __restrict__ gb0, float* __restrict__ gb1, int64_t slab_stride, int32_t* __restrict__ tick,
     const float* __restrict__ fslab, int fslab_w, int nfwd, float* __restrict__ gwo, float* __restrict__ gbo,
-    uint64_t* __restrict__ stamps, int nt_slab) {
+    uint64_t* __restrict__ stamps, int wt) {
   using L = Bwd4Lds<K0>;
   constexpr int NXB = L::NXB, KC = HH / 32, NFW = K0 / 32, NFB = K0 / 16;
   constexpr int DPW = bwdimg::D2_PIECES / 4;    // dact2 LDS-DMA pieces per producer wave and tile (8)
@@ -770,7 +704,7 @@ __global__ __launch_bounds__(512) void mlp_bwd4_kernel(
     HAR_STAMP(8, 34)
     if (n > 0) tile_c(n - 1);
     float* w0o = gw0 + (size_t)slice * slab_stride;
-    if (nt_slab == 2) {  // write-through (see the consumers' slab stores)
+    if (wt) {  // write-through (see the consumers' slab stores)
       const __amdgpu_buffer_rsrc_t rs = wt_rsrc(gw0);
 #pragma unroll
       for (int f = 0; f < NFB; ++f)
@@ -924,18 +858,16 @@ __global__ __launch_bounds__(512) void mlp_bwd4_kernel(
     // (staging both roles' partials through an LDS image and storing whole rows measured 0.5 us slower
     // per step on one box: 0.0540 / 0.0536 / 0.0535 vs 0.0530 / 0.0532 / 0.0530 ms, gpurun_out/ab_epi)
     float* w1o = gw1 + (size_t)slice * slab_stride;
-    // nt_slab: 1 nontemporal, 2 write-through (sc1: the slabs are not left dirty in L2 for the reduction
-    // launch's boundary), 0 plain
+    // wt: write-through (sc1: the slabs are not left dirty in L2 for the reduction launch's boundary;
+    // profiles/r6/mlp_write_through_ab.md), else plain (offsets past 32 bits)
     const __amdgpu_buffer_rsrc_t w1rs = wt_rsrc(gw1);
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
       for (int u = 0; u < 4; ++u)
-        if (nt_slab == 2)
+        if (wt)
           wt_store16(w1rs, (uint32_t)(((size_t)slice * slab_stride + (size_t)(16 * (4 * pw + j) + c16) * HH + qu0 + 16 * u + 4 * g) * 4),
                      __builtin_bit_cast(u32x4_t, acc1[j][u]));
-        else if (nt_slab)
-          nt_store16(w1o + (size_t)(16 * (4 * pw + j) + c16) * HH + qu0 + 16 * u + 4 * g, __builtin_bit_cast(u32x4_t, acc1[j][u]));
         else
           *reinterpret_cast<f32x4_t*>(w1o + (size_t)(16 * (4 * pw + j) + c16) * HH + qu0 + 16 * u + 4 * g) = acc1[j][u];
     if (g == 0) gb1[(size_t)slice * slab_stride + 16 * (4 * q + pw) + c16] = accb[0];
@@ -945,63 +877,35 @@ __global__ __launch_bounds__(512) void mlp_bwd4_kernel(
   HAR_STAMP_REAL(8, 39)
 }
 
-// HAR_MLP_FWD_STAGGER=1: waves 4..7 run their softmax after the MFMA stages (off by default)
-static int fwd_stagger() {
-  static const int v = [] {
-    const char* e = getenv("HAR_MLP_FWD_STAGGER");
-    return e ? atoi(e) : 0;  // measured slower (fwd 21.9 vs 21.1 us, profiles/r5/mlp_fwd_variants.md)
-  }();
-  return v;
-}
-
 template <int K0>
 void launch_fwd3(const bf16_t* X, bf16_t* Wf, const float* b0, const float* b1, const bf16_t* Wo,
                  const float* bo, const int32_t* labels, int B, int C, float scale, bf16_t* dact2,
                  float* slab, float* bl, int32_t* bc, int nwg, hipStream_t s) {
-  static const int fill = [] {
-    const char* e = getenv("HAR_MLP_FWD_FILL");
-    return e ? atoi(e) : 0;
-  }();
-  auto k = g_har_mlp_stamps ? mlp_fwd3_kernel<K0, true>
-           : fill == 1      ? mlp_fwd3_kernel<K0, false, false, 1>
-           : fill == 2      ? mlp_fwd3_kernel<K0, false, false, 2>
-           : fill >= 3      ? mlp_fwd3_kernel<K0, false, false, 3>
-                            : mlp_fwd3_kernel<K0, false>;
-  // dact2 / dWout slab stores write-through (sc1; HAR_MLP_WT=0: plain / nontemporal): the 33.5 MB of
-  // dact2 are then not dirty in the L2s when the backward launches — forward 22.0 -> 19.3 us, step
-  // 0.0571 -> 0.0540 ms (profiles/r6/mlp_write_through_ab.md)
-  static const int wt = [] {
-    const char* e = getenv("HAR_MLP_WT");
-    return e ? atoi(e) : 1;
-  }();
-  const int wtl = (wt & 1) && (size_t)B * HH * 2 < 0x7fffffffu ? 1 : 0;  // (32-bit buffer offsets)
-  k<<<nwg, 512, FWD_LDS, s>>>(X, Wf, b0, b1, Wo, bo, labels, B, C, scale, dact2, slab, bl, bc, g_har_mlp_stamps,
-                              fwd_stagger(), wtl);
+  auto k = g_har_mlp_stamps ? mlp_fwd3_kernel<K0, true> : mlp_fwd3_kernel<K0, false>;
+  // dact2 / dWout slab stores write-through (sc1): the 33.5 MB of dact2 are then not dirty in the L2s
+  // when the backward launches — forward 22.0 -> 19.3 us, step 0.0571 -> 0.0540 ms
+  // (profiles/r6/mlp_write_through_ab.md); plain / nontemporal stores where the offsets pass 32 bits
+  const int wt = (size_t)B * HH * 2 < 0x7fffffffu ? 1 : 0;  // (32-bit buffer offsets)
+  k<<<nwg, 512, FWD_LDS, s>>>(X, Wf, b0, b1, Wo, bo, labels, B, C, scale, dact2, slab, bl, bc, g_har_mlp_stamps, wt);
 }
 
 template <int K0>
 void launch_fwd3_infer(const bf16_t* X, bf16_t* Wf, const float* b0, const float* b1, const bf16_t* Wo,
                        const float* bo, int B, int C, float* logits, int32_t* pred, int nwg, hipStream_t s) {
   mlp_fwd3_kernel<K0, false, true><<<nwg, 512, FWD_LDS, s>>>(X, Wf, b0, b1, Wo, bo, nullptr, B, C, 1.f, nullptr,
-                                                              logits, nullptr, pred, nullptr, fwd_stagger(), 0);
+                                                              logits, nullptr, pred, nullptr, 0);
 }
 
 template <int K0>
 void launch_bwd4(const bf16_t* dact2, const bf16_t* X, const bf16_t* Wf, const float* b0, int B, int S, float* gw1,
                  float* gw0, float* gb0, float* gb1, int64_t stride, int32_t* tick, const float* fslab, int fslab_w,
                  int nfwd, float* gwo, float* gbo, hipStream_t s) {
-  // HAR_MLP_BWD_NT=1: the dW1 partial slabs written with nontemporal stores
-  static const int nt = [] {
-    // the dW1 / dW0 partial slabs: 2 write-through (default: not dirty in L2 at the reduction's launch),
-    // 1 nontemporal, 0 plain
-    const char* e = getenv("HAR_MLP_BWD_NT");
-    return e ? atoi(e) : 2;
-  }();
   auto k = g_har_mlp_stamps ? mlp_bwd4_kernel<K0, true> : mlp_bwd4_kernel<K0, false>;
-  const int ntl = nt == 2 && (size_t)S * stride * 4 >= 0x7fffffffu ? 0 : nt;  // (32-bit buffer offsets)
+  // the dW1 / dW0 partial slabs write-through (not dirty in L2 at the reduction's launch)
+  const int wt = (size_t)S * stride * 4 < 0x7fffffffu ? 1 : 0;  // (32-bit buffer offsets)
   k<<<S * BQ, 512, Bwd4Lds<K0>::bytes, s>>>(dact2, X, Wf, b0, B, S, gw1, gw0, gb0, gb1, stride, tick, fslab, fslab_w,
                                            nfwd, gwo, gbo, g_har_mlp_stamps ? g_har_mlp_stamps + STAMP_BWD_OFF : nullptr,
-                                           ntl);
+                                           wt);
 }
 
 }  // namespace

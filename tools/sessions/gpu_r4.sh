@@ -17,8 +17,6 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -k "$KEXPR" -q -x --timeout 2
 rc=$?; tail -4 "$OUT/pytest.log"; fatal $rc pytest
 timeout -k 10 200 python -u tools/mlp_phase_probe.py 65536 256 > "$OUT/probe.txt" 2>&1
 rc=$?; grep -v amdgpu.ids "$OUT/probe.txt"; fatal $rc probe
-HAR_MLP_BWD=3 timeout -k 10 200 python -u tools/mlp_phase_probe.py 65536 > "$OUT/probe_bwd3.txt" 2>&1
-rc=$?; grep -v amdgpu.ids "$OUT/probe_bwd3.txt" | sed 's/^/[bwd3] /'; fatal $rc probe_bwd3
 timeout -k 10 200 python -u tools/mlp_phase_probe.py --stamps > "$OUT/stamps.txt" 2>&1
 rc=$?; grep -E -- "---|prologue|epilogue|total|clock|tile 4" "$OUT/stamps.txt"; fatal $rc stamps
 timeout -k 10 240 python -u tools/mlp_fit_probe.py > "$OUT/fit_probe.txt" 2>&1

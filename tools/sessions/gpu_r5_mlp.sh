@@ -11,10 +11,11 @@ fatal() { if [ "$1" -ne 0 ] && [ "$1" -ne 1 ] && [ "$1" -ne 5 ]; then echo "STEP
 timeout -k 10 300 python -u -m pytest tests -m gpu -k "${2:-mlp or frag or fused or infer}" -x -q --timeout 200 \
     --timeout-method thread -p no:cacheprovider > "$OUT/pytest.log" 2>&1
 rc=$?; tail -3 "$OUT/pytest.log"; fatal $rc pytest
-# probe variants: VARS="A=1 B=2;C=3" (';'-separated env sets; default: the built-in settings)
-IFS=';' read -r -a vars <<< "${VARS:-HAR_MLP_FWD_STAGGER=0}"
+# probe variants: VARS="A=1 B=2;C=3" (';'-separated env sets, "-" = none; default: the built-in settings)
+IFS=';' read -r -a vars <<< "${VARS:--}"
 i=0
 for v in "${vars[@]}"; do
+  [ "$v" = "-" ] && v=""
   env $v timeout -k 10 200 python -u tools/mlp_phase_probe.py 65536 > "$OUT/probe_v$i.txt" 2>&1
   rc=$?; echo "variant $i: $v"; grep -v amdgpu.ids "$OUT/probe_v$i.txt"; fatal $rc probe
   i=$((i + 1))

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round-6 env A/B of the MLP step: the per-kernel probe under each VARS set (';'-separated env sets,
 # "-" = none), interleaved over ROUNDS rounds, then the driver bench command per set.
-#   usage: VARS="-;HAR_MLP_WT=1" gpurun -- bash tools/sessions/gpu_r6_abenv.sh <tag>
+#   usage: VARS="-;NAME=value" bash tools/sessions/gpu_r6_abenv.sh <tag>
 set -u
 ROOT="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}"
 OUT="$ROOT/gpurun_out/r6ab_${1:-x}"
