@@ -8,6 +8,18 @@ So ``layout=0`` is ``A[M,K] . B[N,K]^T`` (forward of a Linear layer),
 Split-K products (``EPI_F32_ATOMIC`` / ``EPI_F32_SLAB``) run ``ceil(K/k_split)``
 workgroup slices; ``EPI_F32_SLAB`` writes each slice's partial tile into its
 own slab (``C + z*slab_stride``) for a deterministic reduction pass.
+
+Argument contract (refused with ``ValueError`` before anything is launched; ``gemm_dispatch`` in
+``gemm.hip`` repeats what it can see from pointers and pitches):
+
+* A, B and C are 16-byte aligned with a contiguous last dimension; ``bias`` and ``rowsum`` are
+  4-byte aligned.
+* The bf16 epilogues (``EPI_BIAS_RELU``, ``EPI_BIAS``, ``EPI_RELU_GRAD``) move 16-byte row vectors
+  of C and of the mask: ``N % 8 == 0``, ``ldc % 8 == 0``, and for ``EPI_RELU_GRAD`` a mask is
+  required, 16-byte aligned, ``ldmask % 8 == 0``, at least M rows of at least N columns.
+* ``rowsum`` goes with the fp32 epilogues only (``EPI_F32``, ``EPI_F32_ATOMIC``, ``EPI_F32_SLAB``,
+  ``EPI_BIAS_F32``).  The kernel could sum the rows next to a bf16 epilogue as well, but no caller
+  does and no test covers it, so the combination is refused rather than left working by accident.
 """
 from __future__ import annotations
 
@@ -57,9 +69,41 @@ def _check(t: torch.Tensor, name: str):
         raise ValueError(f"{name} must be 16-byte aligned")
 
 
+BF16_EPILOGUES = (EPI_BIAS_RELU, EPI_BIAS, EPI_RELU_GRAD)
+
+
+def _check_contract(C, M, N, epi, bias, mask, rowsum, ldc):
+    """The pitch / pointer / presence rules of the module docstring (pure: no device needed)."""
+    if bias is not None and bias.data_ptr() % 4:
+        raise ValueError("bias must be 4-byte aligned")
+    if rowsum is not None and rowsum.data_ptr() % 4:
+        raise ValueError("rowsum must be 4-byte aligned")
+    if epi not in BF16_EPILOGUES:
+        return
+    if rowsum is not None:
+        raise ValueError("rowsum is not supported with a bf16 epilogue")
+    if N % 8:
+        raise ValueError(f"bf16 epilogues need N % 8 == 0 (N={N})")
+    if ldc % 8 or ldc < N:
+        raise ValueError(f"bf16 epilogues need ldc % 8 == 0 and ldc >= N (ldc={ldc})")
+    if epi != EPI_RELU_GRAD:
+        return
+    if mask is None:
+        raise ValueError("EPI_RELU_GRAD needs a mask")
+    if mask.dim() != 2 or mask.stride(-1) != 1:
+        raise ValueError("mask must be 2-D with a contiguous last dimension")
+    if mask.data_ptr() % 16:
+        raise ValueError("mask must be 16-byte aligned")
+    if mask.stride(0) % 8:
+        raise ValueError(f"EPI_RELU_GRAD needs ldmask % 8 == 0 (ldmask={mask.stride(0)})")
+    if mask.shape[0] < M or mask.shape[1] < N:
+        raise ValueError(f"mask{tuple(mask.shape)} is smaller than the output [{M}, {N}]")
+
+
 def _gemm(bf16: bool, A, B, C, M, N, K, layout, epi, bias=None, mask=None, rowsum=None,
           k_split: Optional[int] = None, alpha: float = 1.0, lda=None, ldb=None, ldc=None, tile: int = -1,
           slab_stride: int = 0, slab_stride_rowsum: int = 0):
+    _check_contract(C, M, N, epi, bias, mask, rowsum, C.stride(0) if ldc is None else ldc)
     for t, n in ((A, "A"), (B, "B"), (C, "C")):
         _check(t, n)
     if epi in (EPI_F32_ATOMIC, EPI_F32_SLAB) and k_split is None:

@@ -405,6 +405,18 @@ int gemm_dispatch(const GemmParams& p, int layout, int epi, hipStream_t s) {
   // vector-load alignment contract (checked on the host side as well)
   if ((a_mmajor ? p.M : p.K) % EPV || (b_nmajor ? p.N : p.K) % EPV || p.lda % EPV || p.ldb % EPV) return -2;
   if ((epi == EPI_F32_ATOMIC || epi == EPI_F32_SLAB) && (p.k_split <= 0 || p.k_split % 32)) return -3;
+  // epilogue operands (ops/gemm.py states the contract): bias and rowsum are read / written as floats,
+  // the bf16 epilogues move 16-byte row vectors of C and of the mask, rowsum goes with fp32 epilogues only
+  const auto misaligned = [](const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) != 0; };
+  if (misaligned(p.bias, 4) || misaligned(p.rowsum, 4)) return -7;
+  if (is_bf16_epi(epi)) {
+    if (p.rowsum) return -8;
+    if (p.N % 8 || p.ldc % 8 || p.ldc < p.N) return -6;
+    if (epi == EPI_RELU_GRAD) {
+      if (!p.mask) return -9;
+      if (misaligned(p.mask, 16) || p.ldmask % 8 || p.ldmask < p.N) return -7;
+    }
+  }
   if (!a_mmajor && !b_nmajor) return launch_tile<T, true, true>(p, epi, s);
   if (!a_mmajor && b_nmajor) return launch_tile<T, true, false>(p, epi, s);
   if (a_mmajor && b_nmajor) return launch_tile<T, false, false>(p, epi, s);

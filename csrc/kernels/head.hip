@@ -240,28 +240,49 @@ extern "C" int har_reduce_slabs_multi(int nseg, const float* const* slabs, const
   return 0;
 }
 
+// dynamic LDS of head_fused_kernel at hidden width D: Wout image, dz tiles, dH staging
+constexpr size_t head_lds_bytes(int D) {
+  return (size_t)(32 * (D + 8) + 4 * 16 * DZP + 4 * 16 * (D + 8)) * sizeof(bf16_t);
+}
+constexpr int HEAD_MAX_D = 800;  // the widest multiple of 32 whose images (+ the 32 static bytes) fit 160 KB
+static_assert(head_lds_bytes(HEAD_MAX_D) + 64 <= 160 * 1024 && head_lds_bytes(HEAD_MAX_D + 32) + 64 > 160 * 1024,
+              "HEAD_MAX_D is the widest head that fits the LDS");
+
+// Each instantiation declares the most dynamic LDS it is launched with (past 64 KB from D = 320 on), once.
+template <int DT>
+int launch_head(const bf16_t* H, const bf16_t* W, const float* bias, const int32_t* labels, int B, int D, int C,
+                float scale, bf16_t* dlogits, bf16_t* dH, float* block_loss, int32_t* block_correct, int blocks,
+                hipStream_t s) {
+  static bool attr = [] {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(&head_fused_kernel<DT>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)head_lds_bytes(DT ? DT : HEAD_MAX_D)) == hipSuccess;
+  }();
+  if (!attr) return -4;
+  head_fused_kernel<DT><<<blocks, 256, head_lds_bytes(D), s>>>(H, W, bias, labels, B, D, C, scale, dlogits, dH,
+                                                               block_loss, block_correct);
+  HAR_CHECK_LAUNCH();
+  return 0;
+}
+
 extern "C" int har_head_fused_blocks(int B) { return (int)(((int64_t)B + ROWS - 1) / ROWS); }
 
 extern "C" int har_head_fused(const uint16_t* H, const uint16_t* W, const float* bias, const int32_t* labels, int B,
                               int D, int C, float scale, uint16_t* dlogits, uint16_t* dH, float* block_loss,
                               int32_t* block_correct, hipStream_t s) {
-  if (C > 32 || D % 32 || D > 1024) return -2;
+  if (C < 1 || C > 32 || D < 32 || D % 32) return -2;
+  if (D > HEAD_MAX_D) return -3;
   const int blocks = har_head_fused_blocks(B);
   if (blocks == 0) return 0;
-  const size_t lds = (size_t)(32 * (D + 8) + 4 * 16 * DZP + 4 * 16 * (D + 8)) * sizeof(uint16_t);
-  if (lds > 160 * 1024) return -3;
-#define HEAD_LAUNCH(DT)                                                                                 \
-  head_fused_kernel<DT><<<blocks, 256, lds, s>>>(H, W, bias, labels, B, D, C, scale, dlogits, dH, block_loss, \
-                                                 block_correct)
+#define HEAD_LAUNCH(DT) \
+  return launch_head<DT>(H, W, bias, labels, B, D, C, scale, dlogits, dH, block_loss, block_correct, blocks, s)
   switch (D) {
-    case 128: HEAD_LAUNCH(128); break;
-    case 256: HEAD_LAUNCH(256); break;
-    case 512: HEAD_LAUNCH(512); break;
+    case 128: HEAD_LAUNCH(128);
+    case 256: HEAD_LAUNCH(256);
+    case 512: HEAD_LAUNCH(512);
     default: HEAD_LAUNCH(0);
   }
 #undef HEAD_LAUNCH
-  HAR_CHECK_LAUNCH();
-  return 0;
 }
 
 extern "C" int har_reduce_slabs_grouped(const float* slabs, int S, int64_t n, int64_t lds, float* dst, int G,

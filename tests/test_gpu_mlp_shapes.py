@@ -98,6 +98,10 @@ def _grad_cases():
     cases += [("gemm", [43, 64, 96, C], 77) for C in (1, 16, 17, 31, 32)]
     cases += [("gemm", [65, 64, 64, 6], 77)]
     cases += [("gemm", [43, 256, 256, 6], B) for B in (1, 7, 200, 3793)]
+    # what the generic path exists for: one hidden layer (no dgrad GEMM), three (dgrad chained through both
+    # dbuf halves), and last widths whose fused head takes 105 KB / the first 65 KB (past 64 KB) of LDS
+    cases += [("gemm", [43, 96, 6], 77), ("gemm", [43, 64, 96, 64, 6], 77), ("gemm", [43, 64, 512, 6], 65),
+              ("gemm", [43, 320, 320, 17], 65)]
     return [c + ("rand",) for c in cases]
 
 
