@@ -62,6 +62,11 @@ class RunConfig:
     gbt_max_iter: int = 20
     gbt_max_depth: int = 5
     gbt_step_size: float = 0.1
+    # KNNClassifier (new): exact k-nearest neighbours; --knn-group-col UID adds the leave-one-group-out
+    # accuracy over the training table (one grouped search)
+    knn_k: int = 5
+    knn_weights: str = "uniform"             # uniform | distance
+    knn_group_col: str = ""
     # NaiveBayes / MLP (new)
     nb_model_type: str = "gaussian"
     mlp_hidden: List[int] = field(default_factory=lambda: [128, 128])
@@ -104,6 +109,8 @@ PRESETS: Dict[str, Dict] = {
     "all-numeric": {"classifiers": ["lr", "dt", "rf", "nb", "mlp"], "encoding": "numeric43", "rf_max_depth": 10},
     # gradient-boosted trees on the numeric encoding
     "gbt": {"classifiers": ["gbt"], "encoding": "numeric43"},
+    # exact k-nearest neighbours on the numeric encoding
+    "knn": {"classifiers": ["knn"], "encoding": "numeric43"},
 }
 
 

@@ -12,8 +12,10 @@ Here, for LogisticRegression, all 45 fits are ONE batched device optimization
 resident training matrix, so the two GEMMs of every objective evaluation cover
 all 45 models at once.  DecisionTree / RandomForest grow the trees of all k folds
 as one level-synchronous forest (fold masks multiply the bootstrap weights; split
-candidates come from the whole CV input, labels never); other estimators fit per
-(fold, map) on the device.
+candidates come from the whole CV input, labels never); KNNClassifier scores every
+fold with ONE search of all rows against all rows, the fold ids as exclusion groups
+(maps over ``k`` / ``weights``: one vote per map on the list prefixes); other
+estimators fit per (fold, map) on the device.
 
 Note on the objective: in the reference the CV evaluator is whatever object was
 last assigned to ``evaluator`` — ``RegressionEvaluator(metricName="mae")``
@@ -181,6 +183,18 @@ class CrossValidator(Estimator):
             vals = vals.cpu().numpy() if torch.is_tensor(vals) else vals
             for (mi, f), v in zip(index, vals):
                 metrics[mi, f] = v
+        elif hasattr(est, "cv_predictions") and all(set(pm) <= {"k", "weights"} for pm in maps):
+            # k-nearest neighbours: ONE search of all rows against all rows with the fold ids as exclusion
+            # groups at the largest k, one vote per map on the list prefixes (the moments are the whole
+            # table's: features only, never labels — PARITY.md)
+            dev = resolve_device(est.device)
+            fold_t = fold_ids_on(dev)
+            y, pred, raw, K = est.cv_predictions(table, fold_t, maps)
+            in_fold = fold_t[None, :] == torch.arange(k, device=dev)[:, None]             # [k, N]
+            nm = len(maps)
+            vals = ev.evaluate_batched(y, pred.repeat_interleave(k, dim=0), in_fold.repeat(nm, 1), K,
+                                       raw.repeat_interleave(k, dim=0))
+            metrics[:, :] = np.asarray(vals, dtype=np.float64).reshape(nm, k)
         elif hasattr(est, "fit_folds") and not getattr(est, "weightCol", None):
             # trees: every fold's tree(s) in one lock-step build; NaiveBayes: fold masks as row weights
             dev = resolve_device(est.device)

@@ -128,6 +128,13 @@ def _build(md, t, children, device):
         d = _dev(device)
         return NaiveBayesModel(t["pi"].to(d), t["theta"].to(d), t["sigma"].to(d) if "sigma" in t else None,
                                st["modelType"], uid=uid, device=d)
+    if cls == "KNNClassificationModel":
+        from ..models.knn import KNNClassificationModel
+
+        m = KNNClassificationModel.from_state(t, st, md["numClasses"], uid=uid, device=_dev(device))
+        m.featuresCol = p.get("featuresCol", m.featuresCol)
+        m.labelCol = p.get("labelCol", m.labelCol)
+        return m
     if cls == "KMeansModel":
         from ..models.kmeans import KMeansModel
 

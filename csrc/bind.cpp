@@ -715,6 +715,62 @@ PYBIND11_MODULE(_har_native, m) {
     check(har_kmeans_update(&a, S(st)), "kmeans_update");
   });
 
+  // Exact k-nearest neighbours (knn.hip)
+  m.def("knn_query_rows", []() { return har_knn_query_rows(); });
+  m.def("knn_max_k", []() { return har_knn_max_k(); });
+  m.def("knn_max_d", []() { return har_knn_max_d(); });
+  m.def("knn_max_classes", []() { return har_knn_max_classes(); });
+  m.def("knn_max_splits", []() { return har_knn_max_splits(); });
+  m.def("knn_slab_rows", [](int D) {
+    const int r = har_knn_slab_rows(D);
+    check(r < 0 ? r : 0, "knn_slab_rows");
+    return r;
+  });
+  m.def("knn_auto_splits", [](int64_t N, int64_t M, int D) {
+    const int r = har_knn_auto_splits(N, M, D);
+    check(r < 0 ? r : 0, "knn_auto_splits");
+    return r;
+  });
+  m.def("knn_search", [](u Q, int64_t N, u R, u h, int64_t M, int D, int k, int splits, u qgroup, u rgroup, u ps, u pi,
+                         u st) {
+    KnnSearchArgs a{};
+    a.Q = P<const float>(Q);
+    a.N = N;
+    a.R = P<const float>(R);
+    a.h = P<const float>(h);
+    a.M = M;
+    a.D = D;
+    a.k = k;
+    a.splits = splits;
+    a.qgroup = P<const int32_t>(qgroup);
+    a.rgroup = P<const int32_t>(rgroup);
+    a.ps = P<float>(ps);
+    a.pi = P<int32_t>(pi);
+    check(har_knn_search(&a, S(st)), "knn_search");
+  });
+  m.def("knn_merge_vote", [](u ps, u pi, int splits, u Q, int D, int64_t N, int k, int ldk, u idx, u d2, u y, int64_t M,
+                             int C, int weights, u raw, u prob, u pred, u st) {
+    KnnVoteArgs a{};
+    a.ps = P<const float>(ps);
+    a.pi = P<const int32_t>(pi);
+    a.splits = splits;
+    a.Q = P<const float>(Q);
+    a.D = D;
+    a.N = N;
+    a.k = k;
+    a.ldk = ldk;
+    a.idx = P<int32_t>(idx);
+    a.d2 = P<float>(d2);
+    a.y = P<const int32_t>(y);
+    a.M = M;
+    a.C = C;
+    a.weights = weights;
+    a.raw = P<double>(raw);
+    a.prob = P<double>(prob);
+    a.pred = P<int32_t>(pred);
+    check(har_knn_merge_vote(&a, S(st)), "knn_merge_vote");
+  });
+
   // Gaussian mixtures (gmm.hip)
   m.def("gmm_rows_per_block", []() { return har_gmm_rows_per_block(); });
   m.def("gmm_group", [](int D, int K) {

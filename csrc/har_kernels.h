@@ -584,6 +584,57 @@ typedef struct KMeansUpdateArgs {
 } KMeansUpdateArgs;
 int har_kmeans_update(const KMeansUpdateArgs* a, hipStream_t s);
 
+// ---- Exact k-nearest neighbours (knn.hip): queries x references on the fp32 matrix cores, fused top-k ----
+// Working rows Q [N][D], R [M][D] fp32, h [M] = ||R[m]||^2 / 2; the score is s[n][m] = h[m] - <Q[n], R[m]>.
+// The neighbours of a row are its k smallest pairs (s, m) in lexicographic order; a pair with
+// qgroup[n] >= 0 and qgroup[n] == rgroup[m] is skipped; missing entries are (+inf, -1).  Split t of
+// `splits` takes the slabs [t S / splits, (t + 1) S / splits) of the S = ceil(M / har_knn_slab_rows(D))
+// slabs of references and writes its sorted lists to ps / pi [splits][N][k].  1 <= splits <= min(S,
+// har_knn_max_splits()).  Contract codes: -2 bad shape, -4 null pointer.
+typedef struct KnnSearchArgs {
+  const float* Q;
+  int64_t N;
+  const float* R;
+  const float* h;
+  int64_t M;
+  int D, k, splits;
+  const int32_t* qgroup;  // [N] (nullable: nothing is excluded)
+  const int32_t* rgroup;  // [M] (nullable)
+  float* ps;              // [splits][N][k] scores, ascending
+  int32_t* pi;            // [splits][N][k] reference indices
+} KnnSearchArgs;
+int har_knn_search(const KnnSearchArgs* a, hipStream_t s);
+int har_knn_query_rows();
+int har_knn_max_k();
+int har_knn_max_d();
+int har_knn_max_classes();
+int har_knn_max_splits();
+int har_knn_slab_rows(int D);
+// the number of splits the front-end takes when the caller names none: enough workgroups for the 256 CUs
+int har_knn_auto_splits(int64_t N, int64_t M, int D);
+// Per query row.  With ps: the k smallest pairs of the splits' lists -> idx, d2 = float(max(0, ||q||^2 +
+// 2 s)) ([N][ldk], the first k of a row are written); without: idx / d2 are inputs.  With y (labels of the
+// references, classes 0 .. C - 1): class weights over the first k entries (weights 0 = uniform, 1 =
+// 1 / sqrt(d2) with the zero-distance rule) -> raw, prob [N][C] fp64 and pred [N] (each nullable).
+typedef struct KnnVoteArgs {
+  const float* ps;
+  const int32_t* pi;
+  int splits;
+  const float* Q;  // [N][D] (with ps)
+  int D;
+  int64_t N;
+  int k, ldk;
+  int32_t* idx;
+  float* d2;
+  const int32_t* y;  // [M] (nullable: no vote)
+  int64_t M;
+  int C, weights;
+  double* raw;
+  double* prob;
+  int32_t* pred;
+} KnnVoteArgs;
+int har_knn_merge_vote(const KnnVoteArgs* a, hipStream_t s);
+
 // ---- Gaussian mixtures (gmm.hip): full-covariance EM on the fp32 matrix cores ----
 // Working rows Z [N][D] fp32 (standardised by the caller).  Component k: mu [K][D], the upper triangular
 // W_k = L_k^{-T} [K][D][D] (Sigma_k = L_k L_k^T; the kernel reads entries on and above the diagonal only)

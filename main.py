@@ -13,6 +13,7 @@ DecisionTree(+CV), RandomForest(+CV) — plus NaiveBayes and an MLP — and writ
     python main.py --preset rf-deep                  # RF 100 trees x depth 10 on the GPU
     python main.py --preset all-numeric --save-models models/
     python main.py --preset gbt --gbt-max-iter 50    # gradient-boosted trees (K trees per round)
+    python main.py --preset knn --knn-k 5 --knn-group-col UID   # exact k-nearest neighbours + leave-one-group-out
     python main.py --hmm --save-models models/       # + Viterbi-smoothed timeline per classifier (HMMSmoother)
     python main.py --hmm-posterior --hmm-em 10       # + forward-backward posteriors; Baum-Welch-refined transitions
     python main.py --kmeans 6 --save-models models/  # + KMeans clusters, silhouette, purity against the labels
@@ -61,7 +62,11 @@ from har.utils.timing import PhaseTimer, device_sync  # noqa: E402
 
 
 def make_estimator(name: str, cfg: RunConfig, dev, n_features: int, n_classes: int):
-    """``build_estimator`` plus the classifiers added after the reference suite (``gbt``)."""
+    """``build_estimator`` plus the classifiers added after the reference suite (``gbt``, ``knn``)."""
+    if name == "knn":
+        from har.models.knn import KNNClassifier
+
+        return KNNClassifier(k=cfg.knn_k, weights=cfg.knn_weights, featuresCol="features", labelCol="label", device=dev)
     if name == "gbt":
         from har.models.gbt import GBTClassifier
 
@@ -210,7 +215,7 @@ def run(cfg: RunConfig, ctx=None) -> dict:
 
     if dev.type == "cuda":
         with timer.phase("device_warmup"):
-            suite_names = [c for c in cfg.classifiers if c != "gbt"]
+            suite_names = [c for c in cfg.classifiers if c not in ("gbt", "knn")]
             if suite_names:
                 warm_up_device(dev, train, cfg, classifiers=suite_names, test=test_data)
             if "gbt" in cfg.classifiers:  # the GBT kernels' code objects, on 256 rows and 2 rounds
@@ -219,6 +224,12 @@ def run(cfg: RunConfig, ctx=None) -> dict:
                 est.maxIter = 2
                 wm = est.fit(small)
                 wm.predict_all(wm.features_input(test_data))
+                device_sync(dev)
+            if "knn" in cfg.classifiers:  # the kNN kernels' code objects, on 256 rows (plain and grouped search)
+                small = train.head(min(256, train.count()))
+                est = make_estimator("knn", cfg, dev, n_feature_columns(small), len(train["label"].meta["vocab"]))
+                est.fit(small).predict_all(features_tensor(test_data, "features", dev))
+                est.leave_group_out(small)
                 device_sync(dev)
             if cfg.kmeans:  # the K-means / silhouette code objects, on 256 rows and 2 iterations
                 from har.evaluation.evaluators import ClusteringEvaluator
@@ -292,6 +303,15 @@ def run(cfg: RunConfig, ctx=None) -> dict:
             r = evaluate_all(y_test, pred, raw_pred, n_classes)
         evaluation_block(log, r)
         hmm_rec = {}
+        if name == "knn" and cfg.knn_group_col:  # one grouped search of the training table against itself
+            with timer.phase("leave_group_out:knn"):
+                lgo = est.leave_group_out(train, cfg.knn_group_col)
+                y_tr = torch.as_tensor(train["label"].data.astype(np.int64), device=lgo.device)
+                hmm_rec["leave_group_out_accuracy"] = float((lgo == y_tr).double().mean())
+            hmm_rec["leave_group_out_groups"] = int(len(np.unique(np.asarray(train[cfg.knn_group_col].data))))
+            log.print("Leave-one-%s-out Accuracy = %g  (%d groups, %d training rows)"
+                      % (cfg.knn_group_col, hmm_rec["leave_group_out_accuracy"], hmm_rec["leave_group_out_groups"],
+                         train.count()))
         if em_pending:  # Baum-Welch on the first fitted classifier's probabilities of the training rows
             em_pending = False
             hmm_est.emIter = cfg.hmm_em_iter

@@ -243,7 +243,7 @@ def run_gmm(args, model, table, labels, dev, t0) -> dict:
 def main(argv=None):
     ap = argparse.ArgumentParser(description="Batch inference from models saved by main.py --save-models")
     ap.add_argument("--models", required=True, help="directory written by main.py --save-models")
-    ap.add_argument("--model", default="rf", help="sub-directory name: lr, lrcv, dt, dtcv, rf, rfcv, nb, mlp, gbt, kmeans, gmm")
+    ap.add_argument("--model", default="rf", help="sub-directory name: lr, lrcv, dt, dtcv, rf, rfcv, nb, mlp, gbt, knn, kmeans, gmm")
     ap.add_argument("--data", default=DEFAULT_WISDM)
     ap.add_argument("--out", default="")
     ap.add_argument("--device", default="auto")
