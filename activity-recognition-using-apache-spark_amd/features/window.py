@@ -133,7 +133,7 @@ def _window_features_into(stream: torch.Tensor, window: int, stride: int, hz: fl
     except RuntimeError as e:
         if not _is_wide(e):
             raise
-        out[:, :n_features(A)] = _wide_windows(s, window, stride, hz)
+        out[:nw, :n_features(A)] = _wide_windows(s, window, stride, hz)
 
 
 def window_features(stream: torch.Tensor, window: int, stride: int, hz: float) -> torch.Tensor:
@@ -183,20 +183,29 @@ def window_features_mlp(stream: torch.Tensor, window: int, stride: int, hz: floa
         return res
     if out is None:
         out = torch.empty(nw, in_pad, dtype=torch.bfloat16, device=stream.device)
+    elif out.dtype != torch.bfloat16 or out.dim() != 2 or out.shape[0] < nw or out.shape[1] < in_pad or \
+            out.stride(1) != 1 or out.device != stream.device:
+        raise ValueError(f"out must be bf16 rows [>= {nw}, >= {in_pad}] with unit column stride on {stream.device}")
     if nw:
         s = stream.contiguous().float()
         m = mean.float().contiguous()
         r = inv_std.float().contiguous()
+        # the kernel writes rows ``in_pad`` apart and zeroes every column up to its row pitch: a wider ``out``
+        # (row pitch != in_pad) takes its rows through a staging buffer, so its further columns stay untouched
+        rows = out[:nw, :in_pad]
+        dst = rows if out.stride(0) == in_pad else torch.empty(nw, in_pad, dtype=torch.bfloat16, device=out.device)
         try:
             _native.kernels().window_features_mlp(s.data_ptr(), S, A, window, stride, nw, float(hz), m.data_ptr(),
-                                                  r.data_ptr(), float(nan_value), out.data_ptr(), in_pad,
+                                                  r.data_ptr(), float(nan_value), dst.data_ptr(), in_pad,
                                                   _native.stream_ptr())
         except RuntimeError as e:
             if not _is_wide(e):
                 raise
             X = torch.nan_to_num(_wide_windows(s, window, stride, hz), nan=nan_value)
-            out.zero_()
-            out[:, :F] = ((X - m) * r).to(torch.bfloat16)
+            dst.zero_()
+            dst[:, :F] = ((X - m) * r).to(torch.bfloat16)
+        if dst is not rows:
+            rows.copy_(dst)
     return out
 
 
