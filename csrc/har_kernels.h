@@ -97,8 +97,9 @@ int har_head_fused_blocks(int B);
 // Fused 2-hidden-layer MLP forward + head + head weight gradient (mlp_fused.hip):
 // X [B][K0] bf16 (K0 = 32/64), W0 [H][K0], W1 [H][H], Wo [>=16][H] bf16 (H = 128/256),
 // fp32 biases, C <= 16 classes, B % 16 == 0.  Writes h1 and dact2 = (dz . Wo) * (h2 > 0)
-// ([B][H] bf16), per-workgroup slabs [grid][16*H + 16] (dWout rows 0..15, dbout 0..15)
-// and per-workgroup loss / #correct.  Grid size: har_mlp_fwd_head_grid(B).
+// ([B][H] bf16), per-workgroup slabs of pitch 16*H + 16 + H floats (dWout rows 0..15, dbout 0..15;
+// the last H floats of a slab are not written) and per-workgroup loss / #correct.  Grid size:
+// har_mlp_fwd_head_grid(B).
 int har_mlp_fwd_head(const uint16_t* X, int K0, const uint16_t* W0, const float* b0, const uint16_t* W1,
                      const float* b1, int H, const uint16_t* Wo, const float* bo, const int32_t* labels, int B,
                      int C, float scale, uint16_t* h1, uint16_t* dact, float* slab, float* block_loss,
