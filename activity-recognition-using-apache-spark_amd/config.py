@@ -27,7 +27,7 @@ class RunConfig:
     data: str = DEFAULT_WISDM
     out_dir: str = "wisdm_main_ver_0.0/main_result"
     plot_dir: str = "wisdm_main_ver_0.0/plot"
-    encoding: str = "reference"            # reference | numeric43
+    encoding: str = "reference"            # reference | numeric43 | rocket | numeric43+rocket
     classifiers: List[str] = field(default_factory=lambda: ["lr", "lrcv", "dt", "dtcv", "rf", "rfcv"])
     split: List[float] = field(default_factory=lambda: [0.7, 0.3])
     seed: int = 2018
@@ -41,10 +41,15 @@ class RunConfig:
     hz: float = 20.0                       # WISDM v1.1 sampling rate (BASELINE.json configs use 50)
     window_sec: float = 10.0               # WISDM window length
     overlap: float = 0.0                   # fraction of a window shared with the next one
+    # RocketFeaturizer (new, opt-in, needs --raw): --rocket N appends ~N MiniRocket-style RKT* columns
+    rocket: int = 0
     # LogisticRegression (main.py:115)
     lr_max_iter: int = 20
     lr_reg: float = 0.3
     lr_elastic_net: float = 0.0
+    # armijo (default) | wolfe: the uncentred RKT* columns (mean / std up to ~30) need the Wolfe search, the
+    # batched Armijo trials reject every step from the start there
+    lr_line_search: str = "armijo"
     # CrossValidator (main.py:202-212)
     cv_folds: int = 5
     cv_reg_grid: List[float] = field(default_factory=lambda: [0.1, 0.3, 0.5])
@@ -111,6 +116,9 @@ PRESETS: Dict[str, Dict] = {
     "gbt": {"classifiers": ["gbt"], "encoding": "numeric43"},
     # exact k-nearest neighbours on the numeric encoding
     "knn": {"classifiers": ["knn"], "encoding": "numeric43"},
+    # convolutional window features of a raw stream (--raw PATH) under logistic regression
+    "rocket": {"classifiers": ["lr"], "encoding": "rocket", "rocket": 1680, "lr_max_iter": 100, "lr_reg": 0.01,
+               "lr_line_search": "wolfe"},
 }
 
 
@@ -156,6 +164,10 @@ def config_from_args(argv=None) -> RunConfig:
         v = getattr(a, f.name)
         if v is not None:
             setattr(cfg, f.name, v)
+    if cfg.rocket < 0 or (cfg.rocket > 0 and not cfg.raw):
+        ap.error("--rocket N (and the rocket preset) featurize a raw stream: give --raw PATH and N > 0")
+    if "rocket" in cfg.encoding and cfg.rocket == 0:
+        ap.error(f"--encoding {cfg.encoding} needs --rocket N")
     if cfg.hmm_posterior or cfg.hmm_em_iter > 0:  # both are switches OF the smoother
         cfg.hmm = True
     return cfg

@@ -95,7 +95,30 @@ def featurize_starts(xyz: torch.Tensor, starts: torch.Tensor, window: int, hz: f
     return f[:, :len(WISDM43)]
 
 
-def _featurize_dp(ctx, xyz_host: np.ndarray, starts: np.ndarray, window: int, hz: float, device) -> torch.Tensor:
+def rocket_starts(xyz: torch.Tensor, starts: torch.Tensor, window: int, model) -> torch.Tensor:
+    """[n, F] rocket features (``features.rocket.RocketModel``) of the windows at ``starts``: the same gather
+    as ``featurize_starts``, the windows back to back."""
+    if starts.numel() == 0:
+        return torch.zeros(0, model.num_features, dtype=torch.float32, device=xyz.device)
+    idx = (starts.view(-1, 1) + torch.arange(window, device=xyz.device).view(1, -1)).reshape(-1)
+    return model.transform(xyz.index_select(0, idx).contiguous(), stride=window)
+
+
+def fit_rocket(xyz_host: np.ndarray, starts: np.ndarray, hz: float, window_sec: float, overlap: float,
+               num_features: int, seed: int = 2018):
+    """Fit a ``RocketModel`` on ALL windows of the file (features only, never labels).  The fit runs on the
+    host whatever the device and the rank count, so every rank and every device draw the same parameters."""
+    from .rocket import RocketFeaturizer
+
+    fz = RocketFeaturizer(hz=hz, seconds=window_sec, overlap=overlap, num_features=num_features, seed=seed)
+    idx = (starts.reshape(-1, 1) + np.arange(fz.window).reshape(1, -1)).reshape(-1)
+    model = fz.fit(torch.as_tensor(xyz_host[idx]))
+    model.stride = fz.stride
+    return model
+
+
+def _featurize_dp(ctx, xyz_host: np.ndarray, starts: np.ndarray, window: int, hz: float, device,
+                  rocket=None) -> torch.Tensor:
     """Rank r featurizes the windows starting in its contiguous sample shard; the last window of a
     shard may run into the next rank's samples: one halo exchange of window - 1 samples."""
     from ..parallel import comm
@@ -108,6 +131,8 @@ def _featurize_dp(ctx, xyz_host: np.ndarray, starts: np.ndarray, window: int, hz
     ext = torch.cat([local, exchange_halo(ctx, local, window - 1, lens)], 0)
     mine = starts[(starts >= lo) & (starts < hi)] - lo
     f = featurize_starts(ext, torch.as_tensor(mine, device=device), window, hz)
+    if rocket is not None:
+        f = torch.cat([f, rocket_starts(ext, torch.as_tensor(mine, device=device), window, rocket)], 1)
     counts = [int(((starts >= (S * r) // ctx.world_size) & (starts < (S * (r + 1)) // ctx.world_size)).sum())
               for r in range(ctx.world_size)]
     pad = torch.zeros(max(counts), f.shape[1], dtype=f.dtype, device=f.device)
@@ -119,8 +144,12 @@ def _featurize_dp(ctx, xyz_host: np.ndarray, starts: np.ndarray, window: int, hz
 
 
 def raw_to_table(path: str, hz: float = 20.0, window_sec: float = 10.0, overlap: float = 0.0, device=None,
-                 ctx=None) -> Table:
-    """Raw rows -> the WISDM transformed table (one row per window, columns of ``wisdm_data.csv:1``)."""
+                 ctx=None, rocket=None) -> Table:
+    """Raw rows -> the WISDM transformed table (one row per window, columns of ``wisdm_data.csv:1``).
+
+    ``rocket``: a feature count (a ``RocketModel`` is fitted on all windows of the file, see ``fit_rocket``) or
+    a fitted ``RocketModel`` (serving); its ``RKT*`` double columns are appended and the model is returned as
+    the table's ``rocket_model`` attribute.  ``None``: the table is exactly the WISDM one."""
     user, act, ts, xyz = read_raw(path)
     window = int(round(hz * window_sec))
     stride = max(1, int(round(window * (1.0 - overlap))))
@@ -128,10 +157,19 @@ def raw_to_table(path: str, hz: float = 20.0, window_sec: float = 10.0, overlap:
         raise ValueError("window must hold at least 3 samples")
     starts, _ = window_starts(user, act, window, stride)
     dev = torch.device(device) if device is not None else torch.device("cpu")
+    if rocket is not None and not hasattr(rocket, "transform"):
+        if len(starts) == 0:
+            raise ValueError(f"{path}: no whole window to fit the rocket transform on")
+        rocket = fit_rocket(xyz, starts, hz, window_sec, overlap, int(rocket))
+    if rocket is not None and rocket.window != window:
+        raise ValueError(f"the rocket model is for windows of {rocket.window} samples, not {window}")
     if ctx is not None and ctx.is_distributed:
-        F = _featurize_dp(ctx, xyz, starts, window, hz, dev)
+        F = _featurize_dp(ctx, xyz, starts, window, hz, dev, rocket)
     else:
-        F = featurize_starts(torch.as_tensor(xyz).to(dev), torch.as_tensor(starts, device=dev), window, hz)
+        xd, sd = torch.as_tensor(xyz).to(dev), torch.as_tensor(starts, device=dev)
+        F = featurize_starts(xd, sd, window, hz)
+        if rocket is not None:
+            F = torch.cat([F, rocket_starts(xd, sd, window, rocket)], 1)
     F = F.double().cpu().numpy()
     n = len(starts)
     cols = [Column("UID", "int", np.arange(n, dtype=np.int64)), Column("USER", "int", user[starts])]
@@ -143,7 +181,13 @@ def raw_to_table(path: str, hz: float = 20.0, window_sec: float = 10.0, overlap:
         else:
             cols.append(Column(name, "double", F[:, j].copy()))
     cols.append(Column("ACTIVITY", "string", np.asarray(act[starts], dtype=object)))
-    return Table(cols)
+    if rocket is None:
+        return Table(cols)
+    for j, name in enumerate(rocket.names):
+        cols.append(Column(name, "double", F[:, len(WISDM43) + j].copy()))
+    table = Table(cols)
+    table.rocket_model = rocket
+    return table
 
 
 def write_synthetic_raw(path: str, n_windows: int = 400, users: int = 6, seed: int = 2018, hz: float = 20.0,

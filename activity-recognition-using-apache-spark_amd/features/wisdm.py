@@ -8,6 +8,8 @@
 * ``numeric43`` — all 43 WISDM features as numbers (``?`` -> -1, which keeps the
   "no peak found" signal): X0..Z9, XAVG..ZAVG, XPEAK..ZPEAK, the deviations and
   RESULTANT.  This is the encoding the MLP and the deep forests use.
+* ``rocket`` / ``numeric43+rocket`` — the ``RKT*`` convolutional columns of ``raw_to_table(rocket=...)``
+  (``features.rocket``), alone or behind the 43 numeric features.
 """
 from __future__ import annotations
 
@@ -84,6 +86,19 @@ def numeric43_pipeline() -> Pipeline:
                      VectorAssembler(inputCols=ALL43, outputCol="features")])
 
 
+def rocket_cols(table: Table) -> List[str]:
+    cols = [c for c in table.columns if c.startswith("RKT")]
+    if not cols:
+        raise ValueError("the table has no RKT* columns: the rocket encodings need raw input with --rocket N")
+    return cols
+
+
+def rocket_pipeline(cols: List[str], with43: bool) -> Pipeline:
+    stages = [CastToDouble(PEAK_COLS, -1.0)] if with43 else []
+    return Pipeline(stages + [StringIndexer(inputCol=LABEL_COL, outputCol="label"),
+                              VectorAssembler(inputCols=(ALL43 if with43 else []) + cols, outputCol="features")])
+
+
 def prepare(table: Table, encoding: str = "reference"):
     """(projected table, fitted pipeline model, transformed table)."""
     if encoding == "reference":
@@ -92,6 +107,9 @@ def prepare(table: Table, encoding: str = "reference"):
     elif encoding == "numeric43":
         data = table.drop(["USER"])
         model = numeric43_pipeline().fit(data)
+    elif encoding in ("rocket", "numeric43+rocket"):
+        data = table.drop(["USER"])
+        model = rocket_pipeline(rocket_cols(table), encoding != "rocket").fit(data)
     else:
         raise ValueError(f"unknown encoding {encoding}")
     return data, model, model.transform(data)

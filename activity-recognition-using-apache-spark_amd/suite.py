@@ -59,7 +59,7 @@ def build_estimator(name: str, cfg: RunConfig, dev, n_features: int, n_classes: 
 
     if name == "lr":
         return LogisticRegression(maxIter=cfg.lr_max_iter, regParam=cfg.lr_reg, elasticNetParam=cfg.lr_elastic_net,
-                                  device=dev)
+                                  lineSearch=cfg.lr_line_search, device=dev)
     if name == "dt":
         return DecisionTreeClassifier(featuresCol="features", labelCol="label", maxDepth=cfg.dt_max_depth,
                                       maxBins=cfg.max_bins, device=dev)

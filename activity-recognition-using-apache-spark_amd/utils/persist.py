@@ -152,6 +152,10 @@ def _build(md, t, children, device):
         m.probabilityCol = p.get("probabilityCol", m.probabilityCol)
         m.feature_cols = st.get("feature_cols")
         return m
+    if cls == "RocketModel":
+        from ..features.rocket import RocketModel
+
+        return RocketModel.from_state(t, st, p, uid=uid)
     if cls == "HMMSmootherModel":
         from ..models.hmm import HMMSmootherModel
 

@@ -590,6 +590,14 @@ PYBIND11_MODULE(_har_native, m) {
           "spectral_features_mlp");
   });
   m.def("spectral_max_window", []() { return har_spectral_max_window(); });
+  m.def("rocket_features", [](u stream, int64_t n_samples, int axes, int window, int stride, int64_t n_windows,
+                              int n_dil, int q, u masks, u biases, u out, int ld_out, int col0, u counts, u st) {
+    check(har_rocket_features(P<const float>(stream), n_samples, axes, window, stride, n_windows, n_dil, q,
+                              P<const int>(masks), P<const float>(biases), P<float>(out), ld_out, col0,
+                              P<int>(counts), S(st)),
+          "rocket_features");
+  });
+  m.def("rocket_max_window", [](int axes) { return har_rocket_max_window(axes); });
 
   // gradient-boosted trees (gbt.hip)
   m.def("gbt_grad", [](u margins, u y, u w, int64_t N, int K, u qgh, u block_loss, u st) {

@@ -356,6 +356,21 @@ int har_spectral_features_mlp(const float* stream, int64_t n_samples, int axes, 
                               int ld_out, int col0, hipStream_t s);
 int har_spectral_max_window();
 
+// ---- MiniRocket-style convolutional window features (rocket.hip) ----
+// 84 dilated 9-tap kernels (the 3-subsets of the taps, weight 2 on the subset and -1 elsewhere) at the
+// n_dil dilations 2^e of the window, an axis bit set masks[e][k] and q biases[e][k][i] per combination.
+// Feature (e * 84 + k) * q + i = fp32(count) / fp32(L): the share of the combination's counted positions
+// (all of [0, W) when e + k is even, [4 d, W - 4 d) otherwise) whose convolution exceeds the bias, written
+// as fp32 into columns [col0, col0 + 84 n_dil q) of rows [n_windows][ld_out]; `counts` (nullable) receives
+// the raw int32 counts [n_windows][84 n_dil q].  Contract codes as har_window_features: -2 bad shape (axes
+// not 3, 6 or 9, window < 9, n_dil not the window's), -3 windows past the stream, -4 null pointer or row too
+// narrow, -5 the zero-padded window image (or the count table) does not fit the LDS.
+int har_rocket_features(const float* stream, int64_t n_samples, int axes, int window, int stride,
+                        int64_t n_windows, int n_dil, int q, const int* masks, const float* biases, float* out,
+                        int ld_out, int col0, int* counts, hipStream_t s);
+// the longest window whose padded image fits the kernel's LDS budget (0: unsupported axis count)
+int har_rocket_max_window(int axes);
+
 // ---- trees ----
 // Fused per-level histogram + best split; grid (feature chunks, active nodes).
 // rows/row_w list each node's rows contiguously (node_start/node_count); feats [A][m].

@@ -20,6 +20,7 @@ DecisionTree(+CV), RandomForest(+CV) — plus NaiveBayes and an MLP — and writ
     python main.py --csv-device                      # CSV parsed + dictionary-encoded by the HIP kernels
     python main.py --report                          # + Results table, charts and index.html (report/)
     python main.py --raw raw.csv --hz 20 --window-sec 10 --overlap 0.5   # raw user,activity,timestamp,x,y,z rows
+    python main.py --raw raw.csv --preset rocket --save-models models/    # + MiniRocket-style RKT* columns under LR (models/rocket)
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 main.py   # data parallel over 8 GPUs (RCCL)
 
 Under ``torch.distributed.run`` every rank loads the (small) table and every model is
@@ -171,7 +172,7 @@ def run(cfg: RunConfig, ctx=None) -> dict:
             from har.features.raw import raw_to_table
 
             raw = raw_to_table(cfg.raw, hz=cfg.hz, window_sec=cfg.window_sec, overlap=cfg.overlap, device=dev,
-                               ctx=ctx)
+                               ctx=ctx, rocket=cfg.rocket or None)
             log.print(f"Raw stream {cfg.raw}: {raw.count()} windows of {int(round(cfg.hz * cfg.window_sec))} "
                       f"samples ({cfg.window_sec:g} s at {cfg.hz:g} Hz, overlap {cfg.overlap:g})")
         else:
@@ -354,6 +355,8 @@ def run(cfg: RunConfig, ctx=None) -> dict:
         gmm_rec = run_gmm(cfg, dev, train, test, vocab, timer, log, main_rank)
     if cfg.save_models and main_rank:
         persist.save(pipe_model, os.path.join(cfg.save_models, "pipeline"), labels=vocab)
+        if getattr(raw, "rocket_model", None) is not None:  # predict.py --raw featurizes with the same transform
+            persist.save(raw.rocket_model, os.path.join(cfg.save_models, "rocket"))
         if smoother is not None:
             persist.save(smoother, os.path.join(cfg.save_models, "hmm"), labels=vocab)
     world = ctx.world_size if ctx is not None else 1

@@ -13,6 +13,7 @@ throughput with device-synchronized timers.
     python predict.py --models models/ --model rf --data new_windows.csv --out preds.csv
     python predict.py --models models/ --model mlp --data wisdm_data.csv --csv-device --repeat 20
     python predict.py --models models/ --model rf --smooth hmm --segments-out timeline.csv --out preds.csv
+    python predict.py --models models/ --model lr --raw raw.csv --out preds.csv    # after main.py --raw .. --preset rocket
 
 Output CSV columns: ``row, UID (if present), prediction, label_name, probability``.
 ``--smooth hmm`` (needs ``<models>/hmm``, written by ``main.py --hmm --save-models``) decodes the
@@ -77,7 +78,18 @@ def run(args) -> dict:
             raise ValueError(f"unknown smoother {args.smooth!r} (hmm | hmm-posterior)")
         smoother = persist.load(os.path.join(args.models, "hmm"), device=dev)
     t0 = time.perf_counter()
-    raw = read_csv(args.data, device=dev if (args.csv_device and dev.type == "cuda") else None)
+    if args.raw:  # raw sensor rows: the saved window settings and rocket transform, then the saved pipeline
+        from har.features.raw import raw_to_table
+
+        rdir = os.path.join(args.models, "rocket")
+        if not os.path.isdir(rdir):
+            raise FileNotFoundError(f"--raw needs the saved featurizer {rdir}: write it with "
+                                    "main.py --raw PATH --rocket N --save-models DIR")
+        rk = persist.load(rdir, device=dev)
+        raw = raw_to_table(args.raw, hz=rk.hz, window_sec=rk.window / rk.hz, overlap=1.0 - rk.stride / rk.window,
+                           device=dev, rocket=rk)
+    else:
+        raw = read_csv(args.data, device=dev if (args.csv_device and dev.type == "cuda") else None)
     table = encode(pipe, raw, args.handle_invalid)
     if type(model).__name__ == "KMeansModel":
         return run_kmeans(args, model, table, labels, dev, t0)
@@ -245,6 +257,8 @@ def main(argv=None):
     ap.add_argument("--models", required=True, help="directory written by main.py --save-models")
     ap.add_argument("--model", default="rf", help="sub-directory name: lr, lrcv, dt, dtcv, rf, rfcv, nb, mlp, gbt, knn, kmeans, gmm")
     ap.add_argument("--data", default=DEFAULT_WISDM)
+    ap.add_argument("--raw", default="", help="raw user,activity,timestamp,x,y,z rows instead of --data: windowed and "
+                                              "featurized with the saved settings and <models>/rocket")
     ap.add_argument("--out", default="")
     ap.add_argument("--device", default="auto")
     ap.add_argument("--csv-device", action="store_true", help="parse the CSV with the HIP kernels")
