@@ -72,6 +72,9 @@ class RunConfig:
     knn_k: int = 5
     knn_weights: str = "uniform"             # uniform | distance
     knn_group_col: str = ""
+    # RidgeClassifier (new): Gram-moment ridge, the penalty chosen by one-pass k-fold cross-validation
+    ridge_alphas: List[float] = field(default_factory=lambda: [round(10.0 ** (-3 + 6 * i / 9), 12) for i in range(10)])
+    ridge_folds: int = 5
     # NaiveBayes / MLP (new)
     nb_model_type: str = "gaussian"
     mlp_hidden: List[int] = field(default_factory=lambda: [128, 128])
@@ -119,6 +122,8 @@ PRESETS: Dict[str, Dict] = {
     # convolutional window features of a raw stream (--raw PATH) under logistic regression
     "rocket": {"classifiers": ["lr"], "encoding": "rocket", "rocket": 1680, "lr_max_iter": 100, "lr_reg": 0.01,
                "lr_line_search": "wolfe"},
+    # the same columns under the ridge classifier of the Rocket literature (cross-validated penalty)
+    "rocket-ridge": {"classifiers": ["ridge"], "encoding": "rocket", "rocket": 1680},
 }
 
 

@@ -723,6 +723,55 @@ PYBIND11_MODULE(_har_native, m) {
     check(har_kmeans_update(&a, S(st)), "kmeans_update");
   });
 
+  // Ridge classifier (ridge.hip)
+  m.def("ridge_chunk_rows", []() { return har_ridge_chunk_rows(); });
+  m.def("ridge_panel", []() { return har_ridge_panel(); });
+  m.def("ridge_max_dim", []() { return har_ridge_max_dim(); });
+  m.def("ridge_gram", [](u X, int64_t ldx, u y, u rows, u mean, u inv_std, std::vector<int64_t> off, int D, int K, int cps,
+                         u slabs, u Af, u Aall, bool reduce, u st) {
+    RidgeGramArgs a{};
+    const int F = (int)off.size() - 1;
+    if (F < 1 || F > HAR_RIDGE_MAX_FOLDS) check(-2, "ridge_gram");
+    a.X = P<const float>(X);
+    a.ldx = ldx;
+    a.y = P<const int32_t>(y);
+    a.rows = P<const int32_t>(rows);
+    a.mean = P<const float>(mean);
+    a.inv_std = P<const float>(inv_std);
+    for (int f = 0; f <= F; ++f) a.off[f] = off[f];
+    a.D = D;
+    a.K = K;
+    a.F = F;
+    a.cps = cps;
+    a.slabs = P<double>(slabs);
+    a.Af = P<double>(Af);
+    a.Aall = P<double>(Aall);
+    if (reduce) check(har_ridge_gram_reduce(&a, S(st)), "ridge_gram_reduce");
+    else check(har_ridge_gram(&a, S(st)), "ridge_gram");
+  });
+  m.def("ridge_solve", [](int step, u Af, u Aall, u alphas, int D, int K, int F, int nalpha, int sys0, int nsys, u Sys,
+                          u info, u W64, u W, u b, u st) {
+    RidgeSolveArgs a{};
+    a.Af = P<const double>(Af);
+    a.Aall = P<const double>(Aall);
+    a.alphas = P<const double>(alphas);
+    a.D = D;
+    a.K = K;
+    a.F = F;
+    a.nalpha = nalpha;
+    a.sys0 = sys0;
+    a.nsys = nsys;
+    a.Sys = P<double>(Sys);
+    a.info = P<int32_t>(info);
+    a.W64 = P<double>(W64);
+    a.W = P<float>(W);
+    a.b = P<float>(b);
+    if (step == 0) check(har_ridge_systems(&a, S(st)), "ridge_systems");
+    else if (step == 1) check(har_ridge_cholesky(&a, S(st)), "ridge_cholesky");
+    else if (step == 2) check(har_ridge_backsolve(&a, S(st)), "ridge_backsolve");
+    else check(-2, "ridge_solve");
+  });
+
   // Exact k-nearest neighbours (knn.hip)
   m.def("knn_query_rows", []() { return har_knn_query_rows(); });
   m.def("knn_max_k", []() { return har_knn_max_k(); });

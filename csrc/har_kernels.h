@@ -651,6 +651,60 @@ typedef struct KnnVoteArgs {
 } KnnVoteArgs;
 int har_knn_merge_vote(const KnnVoteArgs* a, hipStream_t s);
 
+// ---- Ridge classifier (ridge.hip): per-fold Gram moments on the fp32 matrix cores, batched fp64 Cholesky ----
+// Augmented row a = [z | T | 1] (Dq = D + K + 1 columns): z = fl32(fl32(x - mean) * inv_std), T[c] = +1 when
+// y == c else -1.  rows [n_total] lists the table rows grouped by fold; fold f owns rows[off[f] .. off[f + 1]).
+// A fold's rows are cut into chunks of har_ridge_chunk_rows() rows from the fold's start; a chunk is one fp32 fma
+// chain per entry in row order, chunk results are added in fp64.  Workgroup (pair, f, split) takes the chunks
+// [split * cps, (split + 1) * cps) of fold f for one 64 x 64 tile pair (ti <= tj) and stores one fp64 slab
+// slabs[((f * smax + split) * pairs + pair)][64][64]; smax = max_f ceil(chunks_f / cps).  ridge_gram_reduce sums
+// the slabs of a fold in split order into Af [F][ldq][ldq] (entries i <= j, ldq = Dq rounded up to 64) and the
+// folds in order into Aall [ldq][ldq].  Contract codes: -2 bad shape, -4 null pointer.
+#define HAR_RIDGE_MAX_FOLDS 16
+typedef struct RidgeGramArgs {
+  const float* X;         // [N][ldx]
+  int64_t ldx;
+  const int32_t* y;       // [N]
+  const int32_t* rows;    // [off[F]] row indices (< N) grouped by fold
+  const float* mean;      // [D]
+  const float* inv_std;   // [D]
+  int64_t off[HAR_RIDGE_MAX_FOLDS + 1];
+  int D, K, F;
+  int cps;                // chunks per workgroup (>= 1)
+  double* slabs;
+  double* Af;
+  double* Aall;
+} RidgeGramArgs;
+int har_ridge_chunk_rows();
+int har_ridge_panel();
+int har_ridge_max_dim();
+int har_ridge_gram(const RidgeGramArgs* a, hipStream_t s);
+int har_ridge_gram_reduce(const RidgeGramArgs* a, hipStream_t s);
+// Systems sys0 .. sys0 + nsys - 1 of the fit's (F > 1 ? F + 1 : 1) * nalpha (system s: fold s / nalpha, the
+// last one or F == 1 meaning "all rows"; alpha s % nalpha).  With n = n_all - n_f and u = A_all - A_f entrywise,
+// entry (r, c), c <= r, c < D, r < D + K of system s is (u[c][r] - (u[c][q] * u[r][q]) / n) (+ alpha when r == c),
+// q = D + K the column of ones; one rounding per operation, the quotient is 0 when n == 0.  Rows r < D are the
+// lower triangle of M, rows D .. D + K - 1 the border Bc^T.  Sys [nsys][ldn][ldn] row-major, ldn = D + K rounded
+// up to 64; everything else of a system's matrix is written as zero.
+typedef struct RidgeSolveArgs {
+  const double* Af;       // [F][ldq][ldq] (null when F == 1)
+  const double* Aall;     // [ldq][ldq]
+  const double* alphas;   // [nalpha]
+  int D, K, F, nalpha;
+  int sys0, nsys;
+  double* Sys;            // [nsys][ldn][ldn]
+  int32_t* info;          // [total systems]: 0, or 1 + the column whose pivot was not positive and finite
+  double* W64;            // [total systems][K][ldn]: the solution before rounding
+  float* W;               // [total systems][K][D]
+  float* b;               // [total systems][K]
+} RidgeSolveArgs;
+int har_ridge_systems(const RidgeSolveArgs* a, hipStream_t s);
+// Blocked right-looking Cholesky of the leading D columns of every system (panel width har_ridge_panel()); the
+// border rows are carried through the triangular solves and end as (L^-1 Bc)^T.  info must be zero on entry.
+int har_ridge_cholesky(const RidgeSolveArgs* a, hipStream_t s);
+// L^T W = Y per (system, class), then b = (t - W^T s) / n; a system with info != 0 gets W = 0, b = 0.
+int har_ridge_backsolve(const RidgeSolveArgs* a, hipStream_t s);
+
 // ---- Gaussian mixtures (gmm.hip): full-covariance EM on the fp32 matrix cores ----
 // Working rows Z [N][D] fp32 (standardised by the caller).  Component k: mu [K][D], the upper triangular
 // W_k = L_k^{-T} [K][D][D] (Sigma_k = L_k L_k^T; the kernel reads entries on and above the diagonal only)

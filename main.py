@@ -21,6 +21,7 @@ DecisionTree(+CV), RandomForest(+CV) — plus NaiveBayes and an MLP — and writ
     python main.py --report                          # + Results table, charts and index.html (report/)
     python main.py --raw raw.csv --hz 20 --window-sec 10 --overlap 0.5   # raw user,activity,timestamp,x,y,z rows
     python main.py --raw raw.csv --preset rocket --save-models models/    # + MiniRocket-style RKT* columns under LR (models/rocket)
+    python main.py --raw raw.csv --preset rocket-ridge --ridge-folds 5    # the same columns under RidgeClassifier (CV-chosen penalty)
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 main.py   # data parallel over 8 GPUs (RCCL)
 
 Under ``torch.distributed.run`` every rank loads the (small) table and every model is
@@ -63,7 +64,12 @@ from har.utils.timing import PhaseTimer, device_sync  # noqa: E402
 
 
 def make_estimator(name: str, cfg: RunConfig, dev, n_features: int, n_classes: int):
-    """``build_estimator`` plus the classifiers added after the reference suite (``gbt``, ``knn``)."""
+    """``build_estimator`` plus the classifiers added after the reference suite (``gbt``, ``knn``, ``ridge``)."""
+    if name == "ridge":
+        from har.models.ridge import RidgeClassifier
+
+        return RidgeClassifier(alphas=cfg.ridge_alphas, numFolds=cfg.ridge_folds, seed=cfg.seed, featuresCol="features",
+                               labelCol="label", device=dev)
     if name == "knn":
         from har.models.knn import KNNClassifier
 
@@ -216,7 +222,7 @@ def run(cfg: RunConfig, ctx=None) -> dict:
 
     if dev.type == "cuda":
         with timer.phase("device_warmup"):
-            suite_names = [c for c in cfg.classifiers if c not in ("gbt", "knn")]
+            suite_names = [c for c in cfg.classifiers if c not in ("gbt", "knn", "ridge")]
             if suite_names:
                 warm_up_device(dev, train, cfg, classifiers=suite_names, test=test_data)
             if "gbt" in cfg.classifiers:  # the GBT kernels' code objects, on 256 rows and 2 rounds
@@ -231,6 +237,12 @@ def run(cfg: RunConfig, ctx=None) -> dict:
                 est = make_estimator("knn", cfg, dev, n_feature_columns(small), len(train["label"].meta["vocab"]))
                 est.fit(small).predict_all(features_tensor(test_data, "features", dev))
                 est.leave_group_out(small)
+                device_sync(dev)
+            if "ridge" in cfg.classifiers:  # the ridge kernels' code objects, on 256 rows, two folds and two alphas
+                small = train.head(min(256, train.count()))
+                est = make_estimator("ridge", cfg, dev, n_feature_columns(small), len(train["label"].meta["vocab"]))
+                est.alphas, est.numFolds = est.alphas[:2], min(2, est.numFolds)
+                est.fit(small).predict_all(features_tensor(test_data, "features", dev))
                 device_sync(dev)
             if cfg.kmeans:  # the K-means / silhouette code objects, on 256 rows and 2 iterations
                 from har.evaluation.evaluators import ClusteringEvaluator

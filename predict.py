@@ -14,6 +14,7 @@ throughput with device-synchronized timers.
     python predict.py --models models/ --model mlp --data wisdm_data.csv --csv-device --repeat 20
     python predict.py --models models/ --model rf --smooth hmm --segments-out timeline.csv --out preds.csv
     python predict.py --models models/ --model lr --raw raw.csv --out preds.csv    # after main.py --raw .. --preset rocket
+    python predict.py --models models/ --model ridge --raw raw.csv --out preds.csv # after main.py --raw .. --preset rocket-ridge
 
 Output CSV columns: ``row, UID (if present), prediction, label_name, probability``.
 ``--smooth hmm`` (needs ``<models>/hmm``, written by ``main.py --hmm --save-models``) decodes the
@@ -255,7 +256,7 @@ def run_gmm(args, model, table, labels, dev, t0) -> dict:
 def main(argv=None):
     ap = argparse.ArgumentParser(description="Batch inference from models saved by main.py --save-models")
     ap.add_argument("--models", required=True, help="directory written by main.py --save-models")
-    ap.add_argument("--model", default="rf", help="sub-directory name: lr, lrcv, dt, dtcv, rf, rfcv, nb, mlp, gbt, knn, kmeans, gmm")
+    ap.add_argument("--model", default="rf", help="sub-directory name: lr, lrcv, dt, dtcv, rf, rfcv, nb, mlp, gbt, knn, ridge, kmeans, gmm")
     ap.add_argument("--data", default=DEFAULT_WISDM)
     ap.add_argument("--raw", default="", help="raw user,activity,timestamp,x,y,z rows instead of --data: windowed and "
                                               "featurized with the saved settings and <models>/rocket")
