@@ -27,7 +27,7 @@ class RunConfig:
     data: str = DEFAULT_WISDM
     out_dir: str = "wisdm_main_ver_0.0/main_result"
     plot_dir: str = "wisdm_main_ver_0.0/plot"
-    encoding: str = "reference"            # reference | numeric43 | rocket | numeric43+rocket
+    encoding: str = "reference"            # reference | numeric43 | rocket | numeric43+rocket | raw
     classifiers: List[str] = field(default_factory=lambda: ["lr", "lrcv", "dt", "dtcv", "rf", "rfcv"])
     split: List[float] = field(default_factory=lambda: [0.7, 0.3])
     seed: int = 2018
@@ -72,6 +72,13 @@ class RunConfig:
     knn_k: int = 5
     knn_weights: str = "uniform"             # uniform | distance
     knn_group_col: str = ""
+    # DTWClassifier (new, needs --raw and --encoding raw): nearest neighbours between raw windows under banded
+    # dynamic time warping; --dtw-group-col USER adds the leave-one-group-out accuracy over the training table
+    dtw_k: int = 1
+    dtw_band: float = 0.1                    # Sakoe-Chiba radius as a fraction of the window
+    dtw_weights: str = "uniform"             # uniform | distance
+    dtw_normalize: str = "none"              # none | zscore (per window and axis)
+    dtw_group_col: str = ""
     # RidgeClassifier (new): Gram-moment ridge, the penalty chosen by one-pass k-fold cross-validation
     ridge_alphas: List[float] = field(default_factory=lambda: [round(10.0 ** (-3 + 6 * i / 9), 12) for i in range(10)])
     ridge_folds: int = 5
@@ -124,6 +131,8 @@ PRESETS: Dict[str, Dict] = {
                "lr_line_search": "wolfe"},
     # the same columns under the ridge classifier of the Rocket literature (cross-validated penalty)
     "rocket-ridge": {"classifiers": ["ridge"], "encoding": "rocket", "rocket": 1680},
+    # nearest neighbours between the raw windows of a stream (--raw PATH) under banded dynamic time warping
+    "dtw": {"classifiers": ["dtw"], "encoding": "raw"},
 }
 
 
@@ -173,6 +182,10 @@ def config_from_args(argv=None) -> RunConfig:
         ap.error("--rocket N (and the rocket preset) featurize a raw stream: give --raw PATH and N > 0")
     if "rocket" in cfg.encoding and cfg.rocket == 0:
         ap.error(f"--encoding {cfg.encoding} needs --rocket N")
+    if (cfg.encoding == "raw" or "dtw" in cfg.classifiers) and not cfg.raw:
+        ap.error("--encoding raw (and the dtw preset) compare the windows of a raw stream: give --raw PATH")
+    if "dtw" in cfg.classifiers and cfg.encoding != "raw":
+        ap.error("the dtw classifier takes --encoding raw")
     if cfg.hmm_posterior or cfg.hmm_em_iter > 0:  # both are switches OF the smoother
         cfg.hmm = True
     return cfg

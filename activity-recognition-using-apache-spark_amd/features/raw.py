@@ -41,6 +41,11 @@ WISDM43 = ([f"{a}{i}" for a in AXES for i in range(NBINS)] + [a + "AVG" for a in
 ACTIVITIES = ("Walking", "Jogging", "Upstairs", "Downstairs", "Sitting", "Standing")
 
 
+def sample_cols(window: int):
+    """Names of the raw-sample columns of ``raw_to_table(samples=True)``, time-major."""
+    return [f"RAW{i}_{a}" for i in range(window) for a in AXES]
+
+
 def read_raw(path: str):
     """(user int64 [S], activity object [S], timestamp int64 [S], xyz float32 [S, 3])."""
     from ..data.csv_io import parse_csv_bytes
@@ -144,12 +149,15 @@ def _featurize_dp(ctx, xyz_host: np.ndarray, starts: np.ndarray, window: int, hz
 
 
 def raw_to_table(path: str, hz: float = 20.0, window_sec: float = 10.0, overlap: float = 0.0, device=None,
-                 ctx=None, rocket=None) -> Table:
+                 ctx=None, rocket=None, samples: bool = False) -> Table:
     """Raw rows -> the WISDM transformed table (one row per window, columns of ``wisdm_data.csv:1``).
 
     ``rocket``: a feature count (a ``RocketModel`` is fitted on all windows of the file, see ``fit_rocket``) or
     a fitted ``RocketModel`` (serving); its ``RKT*`` double columns are appended and the model is returned as
-    the table's ``rocket_model`` attribute.  ``None``: the table is exactly the WISDM one."""
+    the table's ``rocket_model`` attribute.  ``None``: the table is exactly the WISDM one.
+
+    ``samples``: append the samples of every window as ``RAW{i}_{X,Y,Z}`` double columns, time-major (sample i
+    axis a is column ``3 i + a`` of them: the flattened window of ``ops/dtw.py``)."""
     user, act, ts, xyz = read_raw(path)
     window = int(round(hz * window_sec))
     stride = max(1, int(round(window * (1.0 - overlap))))
@@ -181,12 +189,17 @@ def raw_to_table(path: str, hz: float = 20.0, window_sec: float = 10.0, overlap:
         else:
             cols.append(Column(name, "double", F[:, j].copy()))
     cols.append(Column("ACTIVITY", "string", np.asarray(act[starts], dtype=object)))
-    if rocket is None:
-        return Table(cols)
-    for j, name in enumerate(rocket.names):
-        cols.append(Column(name, "double", F[:, len(WISDM43) + j].copy()))
+    if rocket is not None:
+        for j, name in enumerate(rocket.names):
+            cols.append(Column(name, "double", F[:, len(WISDM43) + j].copy()))
+    if samples:   # the same gather as ``featurize_starts``, on the host: windows back to back
+        idx = (starts.reshape(-1, 1) + np.arange(window).reshape(1, -1)).reshape(-1)
+        S = xyz[idx].reshape(n, window * len(AXES)).astype(np.float64)
+        for j, name in enumerate(sample_cols(window)):
+            cols.append(Column(name, "double", S[:, j].copy()))
     table = Table(cols)
-    table.rocket_model = rocket
+    if rocket is not None:
+        table.rocket_model = rocket
     return table
 
 

@@ -10,6 +10,8 @@
   RESULTANT.  This is the encoding the MLP and the deep forests use.
 * ``rocket`` / ``numeric43+rocket`` — the ``RKT*`` convolutional columns of ``raw_to_table(rocket=...)``
   (``features.rocket``), alone or behind the 43 numeric features.
+* ``raw`` — the ``RAW*`` sample columns of ``raw_to_table(samples=True)``, time-major: the flattened window
+  that ``DTWClassifier`` compares as a time series.
 """
 from __future__ import annotations
 
@@ -99,6 +101,18 @@ def rocket_pipeline(cols: List[str], with43: bool) -> Pipeline:
                               VectorAssembler(inputCols=(ALL43 if with43 else []) + cols, outputCol="features")])
 
 
+def raw_cols(table: Table) -> List[str]:
+    cols = [c for c in table.columns if c.startswith("RAW")]
+    if not cols:
+        raise ValueError("the table has no RAW* columns: the raw encoding needs raw input (raw_to_table(samples=True))")
+    return cols
+
+
+def raw_pipeline(cols: List[str]) -> Pipeline:
+    return Pipeline([StringIndexer(inputCol=LABEL_COL, outputCol="label"),
+                     VectorAssembler(inputCols=cols, outputCol="features")])
+
+
 def prepare(table: Table, encoding: str = "reference"):
     """(projected table, fitted pipeline model, transformed table)."""
     if encoding == "reference":
@@ -110,6 +124,9 @@ def prepare(table: Table, encoding: str = "reference"):
     elif encoding in ("rocket", "numeric43+rocket"):
         data = table.drop(["USER"])
         model = rocket_pipeline(rocket_cols(table), encoding != "rocket").fit(data)
+    elif encoding == "raw":   # the window's own samples (DTWClassifier); USER stays for leave-one-subject-out
+        data = table
+        model = raw_pipeline(raw_cols(table)).fit(data)
     else:
         raise ValueError(f"unknown encoding {encoding}")
     return data, model, model.transform(data)

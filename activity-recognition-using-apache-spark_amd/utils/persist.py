@@ -135,6 +135,13 @@ def _build(md, t, children, device):
         m.featuresCol = p.get("featuresCol", m.featuresCol)
         m.labelCol = p.get("labelCol", m.labelCol)
         return m
+    if cls == "DTWClassificationModel":
+        from ..models.dtw import DTWClassificationModel
+
+        m = DTWClassificationModel.from_state(t, st, md["numClasses"], uid=uid, device=_dev(device))
+        m.featuresCol = p.get("featuresCol", m.featuresCol)
+        m.labelCol = p.get("labelCol", m.labelCol)
+        return m
     if cls == "RidgeClassificationModel":
         from ..models.ridge import RidgeClassificationModel
 

@@ -828,6 +828,61 @@ PYBIND11_MODULE(_har_native, m) {
     check(har_knn_merge_vote(&a, S(st)), "knn_merge_vote");
   });
 
+  // Banded dynamic time warping (dtw.hip)
+  m.def("dtw_query_rows", []() { return har_dtw_query_rows(); });
+  m.def("dtw_slab_rows", []() { return har_dtw_slab_rows(); });
+  m.def("dtw_max_w", []() { return har_dtw_max_w(); });
+  m.def("dtw_max_radius", []() { return har_dtw_max_radius(); });
+  m.def("dtw_max_axes", []() { return har_dtw_max_axes(); });
+  m.def("dtw_max_k", []() { return har_dtw_max_k(); });
+  m.def("dtw_max_splits", []() { return har_dtw_max_splits(); });
+  m.def("dtw_auto_splits", [](int64_t N, int64_t M) {
+    const int r = har_dtw_auto_splits(N, M);
+    check(r < 0 ? r : 0, "dtw_auto_splits");
+    return r;
+  });
+  m.def("dtw_cost", [](u Q, int64_t N, u R, int64_t M, int W, int A, int radius, u cost, u st) {
+    DtwArgs a{};
+    a.Q = P<const float>(Q);
+    a.N = N;
+    a.R = P<const float>(R);
+    a.M = M;
+    a.W = W;
+    a.A = A;
+    a.radius = radius;
+    a.cost = P<float>(cost);
+    check(har_dtw_cost(&a, S(st)), "dtw_cost");
+  });
+  m.def("dtw_search", [](u Q, int64_t N, u R, int64_t M, int W, int A, int radius, int k, int splits, u qgroup, u rgroup,
+                         u ps, u pi, u st) {
+    DtwArgs a{};
+    a.Q = P<const float>(Q);
+    a.N = N;
+    a.R = P<const float>(R);
+    a.M = M;
+    a.W = W;
+    a.A = A;
+    a.radius = radius;
+    a.k = k;
+    a.splits = splits;
+    a.qgroup = P<const int32_t>(qgroup);
+    a.rgroup = P<const int32_t>(rgroup);
+    a.ps = P<float>(ps);
+    a.pi = P<int32_t>(pi);
+    check(har_dtw_search(&a, S(st)), "dtw_search");
+  });
+  m.def("dtw_merge", [](u ps, u pi, int splits, int64_t N, int k, u idx, u d2, u st) {
+    DtwMergeArgs a{};
+    a.ps = P<const float>(ps);
+    a.pi = P<const int32_t>(pi);
+    a.splits = splits;
+    a.N = N;
+    a.k = k;
+    a.idx = P<int32_t>(idx);
+    a.d2 = P<float>(d2);
+    check(har_dtw_merge(&a, S(st)), "dtw_merge");
+  });
+
   // Gaussian mixtures (gmm.hip)
   m.def("gmm_rows_per_block", []() { return har_gmm_rows_per_block(); });
   m.def("gmm_group", [](int D, int K) {

@@ -651,6 +651,49 @@ typedef struct KnnVoteArgs {
 } KnnVoteArgs;
 int har_knn_merge_vote(const KnnVoteArgs* a, hipStream_t s);
 
+// ---- Banded dynamic time warping (dtw.hip): one lane per (query, reference) pair of raw windows ----
+// Windows Q [N][W][A], R [M][W][A] fp32, time-major; Sakoe-Chiba radius 0 <= radius <= min(W - 1,
+// har_dtw_max_radius()); the cost of a pair is the squared-cost DTW of har/ops/dtw.py, one fixed fp32 operation
+// sequence.  dtw_cost writes cost [N][M].  dtw_search keeps the k smallest pairs (cost, m) of every query
+// (knn.hip's order, exclusion and missing entries) over the slabs [t S / splits, (t + 1) S / splits) of the S =
+// ceil(M / har_dtw_slab_rows()) slabs of references and writes the sorted lists ps / pi [splits][N][k]; 1 <=
+// splits <= min(S, har_dtw_max_splits()).  dtw_merge takes the k smallest pairs of the splits' lists -> idx, d2
+// [N][k].  Contract codes: -2 bad shape, -4 null pointer.
+typedef struct DtwArgs {
+  const float* Q;
+  int64_t N;
+  const float* R;
+  int64_t M;
+  int W, A, radius;
+  int k, splits;          // dtw_search
+  const int32_t* qgroup;  // [N] (nullable, with rgroup: nothing is excluded)
+  const int32_t* rgroup;  // [M]
+  float* cost;            // [N][M] (dtw_cost)
+  float* ps;              // [splits][N][k] costs, ascending (dtw_search)
+  int32_t* pi;            // [splits][N][k] reference indices
+} DtwArgs;
+int har_dtw_cost(const DtwArgs* a, hipStream_t s);
+int har_dtw_search(const DtwArgs* a, hipStream_t s);
+typedef struct DtwMergeArgs {
+  const float* ps;
+  const int32_t* pi;
+  int splits;
+  int64_t N;
+  int k;
+  int32_t* idx;  // [N][k]
+  float* d2;     // [N][k]
+} DtwMergeArgs;
+int har_dtw_merge(const DtwMergeArgs* a, hipStream_t s);
+int har_dtw_query_rows();
+int har_dtw_slab_rows();
+int har_dtw_max_w();
+int har_dtw_max_radius();
+int har_dtw_max_axes();
+int har_dtw_max_k();
+int har_dtw_max_splits();
+// the number of splits the front-end takes when the caller names none
+int har_dtw_auto_splits(int64_t N, int64_t M);
+
 // ---- Ridge classifier (ridge.hip): per-fold Gram moments on the fp32 matrix cores, batched fp64 Cholesky ----
 // Augmented row a = [z | T | 1] (Dq = D + K + 1 columns): z = fl32(fl32(x - mean) * inv_std), T[c] = +1 when
 // y == c else -1.  rows [n_total] lists the table rows grouped by fold; fold f owns rows[off[f] .. off[f + 1]).

@@ -22,6 +22,7 @@ DecisionTree(+CV), RandomForest(+CV) — plus NaiveBayes and an MLP — and writ
     python main.py --raw raw.csv --hz 20 --window-sec 10 --overlap 0.5   # raw user,activity,timestamp,x,y,z rows
     python main.py --raw raw.csv --preset rocket --save-models models/    # + MiniRocket-style RKT* columns under LR (models/rocket)
     python main.py --raw raw.csv --preset rocket-ridge --ridge-folds 5    # the same columns under RidgeClassifier (CV-chosen penalty)
+    python main.py --raw raw.csv --preset dtw --dtw-group-col USER        # nearest neighbours between raw windows under banded DTW
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 main.py   # data parallel over 8 GPUs (RCCL)
 
 Under ``torch.distributed.run`` every rank loads the (small) table and every model is
@@ -64,7 +65,7 @@ from har.utils.timing import PhaseTimer, device_sync  # noqa: E402
 
 
 def make_estimator(name: str, cfg: RunConfig, dev, n_features: int, n_classes: int):
-    """``build_estimator`` plus the classifiers added after the reference suite (``gbt``, ``knn``, ``ridge``)."""
+    """``build_estimator`` plus the classifiers added after the reference suite (``gbt``, ``knn``, ``ridge``, ``dtw``)."""
     if name == "ridge":
         from har.models.ridge import RidgeClassifier
 
@@ -74,6 +75,11 @@ def make_estimator(name: str, cfg: RunConfig, dev, n_features: int, n_classes: i
         from har.models.knn import KNNClassifier
 
         return KNNClassifier(k=cfg.knn_k, weights=cfg.knn_weights, featuresCol="features", labelCol="label", device=dev)
+    if name == "dtw":
+        from har.models.dtw import DTWClassifier
+
+        return DTWClassifier(k=cfg.dtw_k, band=cfg.dtw_band, weights=cfg.dtw_weights, normalize=cfg.dtw_normalize,
+                             axes=3, featuresCol="features", labelCol="label", device=dev)
     if name == "gbt":
         from har.models.gbt import GBTClassifier
 
@@ -178,7 +184,7 @@ def run(cfg: RunConfig, ctx=None) -> dict:
             from har.features.raw import raw_to_table
 
             raw = raw_to_table(cfg.raw, hz=cfg.hz, window_sec=cfg.window_sec, overlap=cfg.overlap, device=dev,
-                               ctx=ctx, rocket=cfg.rocket or None)
+                               ctx=ctx, rocket=cfg.rocket or None, samples=cfg.encoding == "raw")
             log.print(f"Raw stream {cfg.raw}: {raw.count()} windows of {int(round(cfg.hz * cfg.window_sec))} "
                       f"samples ({cfg.window_sec:g} s at {cfg.hz:g} Hz, overlap {cfg.overlap:g})")
         else:
@@ -222,7 +228,7 @@ def run(cfg: RunConfig, ctx=None) -> dict:
 
     if dev.type == "cuda":
         with timer.phase("device_warmup"):
-            suite_names = [c for c in cfg.classifiers if c not in ("gbt", "knn", "ridge")]
+            suite_names = [c for c in cfg.classifiers if c not in ("gbt", "knn", "ridge", "dtw")]
             if suite_names:
                 warm_up_device(dev, train, cfg, classifiers=suite_names, test=test_data)
             if "gbt" in cfg.classifiers:  # the GBT kernels' code objects, on 256 rows and 2 rounds
@@ -236,6 +242,12 @@ def run(cfg: RunConfig, ctx=None) -> dict:
                 small = train.head(min(256, train.count()))
                 est = make_estimator("knn", cfg, dev, n_feature_columns(small), len(train["label"].meta["vocab"]))
                 est.fit(small).predict_all(features_tensor(test_data, "features", dev))
+                est.leave_group_out(small)
+                device_sync(dev)
+            if "dtw" in cfg.classifiers:  # the DTW kernels' code objects, on 64 windows (plain and grouped search)
+                small = train.head(min(64, train.count()))
+                est = make_estimator("dtw", cfg, dev, n_feature_columns(small), len(train["label"].meta["vocab"]))
+                est.fit(small).predict_all(features_tensor(test_data.head(min(64, test_data.count())), "features", dev))
                 est.leave_group_out(small)
                 device_sync(dev)
             if "ridge" in cfg.classifiers:  # the ridge kernels' code objects, on 256 rows, two folds and two alphas
@@ -325,6 +337,17 @@ def run(cfg: RunConfig, ctx=None) -> dict:
             log.print("Leave-one-%s-out Accuracy = %g  (%d groups, %d training rows)"
                       % (cfg.knn_group_col, hmm_rec["leave_group_out_accuracy"], hmm_rec["leave_group_out_groups"],
                          train.count()))
+        if name == "dtw" and cfg.dtw_group_col:  # one grouped search of the training table against itself
+            with timer.phase("leave_group_out:dtw"):
+                lgo = est.leave_group_out(train, cfg.dtw_group_col)
+                y_tr = torch.as_tensor(train["label"].data.astype(np.int64), device=lgo.device)
+                hmm_rec["leave_group_out_accuracy"] = float((lgo == y_tr).double().mean())
+            hmm_rec["leave_group_out_groups"] = int(len(np.unique(np.asarray(train[cfg.dtw_group_col].data))))
+            log.print("Leave-one-%s-out Accuracy = %g  (%d groups, %d training rows)"
+                      % (cfg.dtw_group_col, hmm_rec["leave_group_out_accuracy"], hmm_rec["leave_group_out_groups"],
+                         train.count()))
+        if name == "dtw":  # predict.py --raw rebuilds the sample columns with these window settings
+            best.raw_settings = {"hz": cfg.hz, "window_sec": cfg.window_sec, "overlap": cfg.overlap}
         if em_pending:  # Baum-Welch on the first fitted classifier's probabilities of the training rows
             em_pending = False
             hmm_est.emIter = cfg.hmm_em_iter

@@ -15,6 +15,7 @@ throughput with device-synchronized timers.
     python predict.py --models models/ --model rf --smooth hmm --segments-out timeline.csv --out preds.csv
     python predict.py --models models/ --model lr --raw raw.csv --out preds.csv    # after main.py --raw .. --preset rocket
     python predict.py --models models/ --model ridge --raw raw.csv --out preds.csv # after main.py --raw .. --preset rocket-ridge
+    python predict.py --models models/ --model dtw --raw raw.csv --out preds.csv   # after main.py --raw .. --preset dtw
 
 Output CSV columns: ``row, UID (if present), prediction, label_name, probability``.
 ``--smooth hmm`` (needs ``<models>/hmm``, written by ``main.py --hmm --save-models``) decodes the
@@ -83,12 +84,17 @@ def run(args) -> dict:
         from har.features.raw import raw_to_table
 
         rdir = os.path.join(args.models, "rocket")
-        if not os.path.isdir(rdir):
+        rs = getattr(model, "raw_settings", None)
+        if rs is not None:  # a DTW model: the windows' own samples, with the saved window settings
+            raw = raw_to_table(args.raw, hz=rs["hz"], window_sec=rs["window_sec"], overlap=rs["overlap"], device=dev,
+                               samples=True)
+        elif not os.path.isdir(rdir):
             raise FileNotFoundError(f"--raw needs the saved featurizer {rdir}: write it with "
                                     "main.py --raw PATH --rocket N --save-models DIR")
-        rk = persist.load(rdir, device=dev)
-        raw = raw_to_table(args.raw, hz=rk.hz, window_sec=rk.window / rk.hz, overlap=1.0 - rk.stride / rk.window,
-                           device=dev, rocket=rk)
+        else:
+            rk = persist.load(rdir, device=dev)
+            raw = raw_to_table(args.raw, hz=rk.hz, window_sec=rk.window / rk.hz, overlap=1.0 - rk.stride / rk.window,
+                               device=dev, rocket=rk)
     else:
         raw = read_csv(args.data, device=dev if (args.csv_device and dev.type == "cuda") else None)
     table = encode(pipe, raw, args.handle_invalid)
@@ -256,7 +262,7 @@ def run_gmm(args, model, table, labels, dev, t0) -> dict:
 def main(argv=None):
     ap = argparse.ArgumentParser(description="Batch inference from models saved by main.py --save-models")
     ap.add_argument("--models", required=True, help="directory written by main.py --save-models")
-    ap.add_argument("--model", default="rf", help="sub-directory name: lr, lrcv, dt, dtcv, rf, rfcv, nb, mlp, gbt, knn, ridge, kmeans, gmm")
+    ap.add_argument("--model", default="rf", help="sub-directory name: lr, lrcv, dt, dtcv, rf, rfcv, nb, mlp, gbt, knn, ridge, dtw, kmeans, gmm")
     ap.add_argument("--data", default=DEFAULT_WISDM)
     ap.add_argument("--raw", default="", help="raw user,activity,timestamp,x,y,z rows instead of --data: windowed and "
                                               "featurized with the saved settings and <models>/rocket")
