@@ -12,6 +12,16 @@ definitions in PyTorch (oracle).
 Feature row for A axes (``feature_names``), WISDM-43 first when A = 3:
 ``[A x 10 bins][avg A][peak A][absdev A][std A][resultant A/3][min A][max A][energy A][corr 3 per triad]``.
 
+Bins of a degenerate range (fp32 kernels).  The kernels bin a sample as ``trunc((x - min) * sc)`` (bin 10,
+``x == max``, folded into bin 9) with one fp32 scale per (window, axis): ``sc = 0`` for a flat axis
+(``max == min``: every sample in bin 0) and otherwise ``sc = min(fl(10 / (max - min)), FLT_MAX)``.  The
+saturation matters only where ``10 / range`` is not a finite fp32 — ``0 < range < 10 / FLT_MAX = 2.94e-38``,
+some normal and every denormal range (the kernels keep fp32 denormals).  On such an axis ``(x - min) * sc``
+stays below 10, so the ten counts are integers >= 0 that sum to the window length, every sample equal to the
+minimum is counted in bin 0, the samples lie in bins ``floor((x - min) * FLT_MAX)`` (the upper bins stay
+empty), and every kernel and output mode (fixed and runtime runs, the fallback kernel, fp32 and MLP rows) gives
+the same counts.  The float64 definition below has no such limit and spreads such an axis over all ten bins.
+
 All of these are time-domain statistics.  The frequency-domain columns (band energies, dominant
 frequency, spectral centroid and entropy: ``features.spectral``, a second HIP kernel that runs the DFT on
 the matrix cores) are opt-in: ``WindowFeaturizer(spectral=True)`` returns ``[time | spectral]`` rows,

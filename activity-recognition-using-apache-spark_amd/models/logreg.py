@@ -409,9 +409,9 @@ class LogisticRegression(Estimator, ClassifierParams):
                                        tol=self.tol)
             xs, fobj, iters, n_evals = res.x, res.f, res.iterations, res.n_evals
             rounds = res.rounds_per_iter
-            # as Spark's objectiveHistory: the start + one entry per iteration the model took (the batch
-            # rows of a model that stopped earlier are cut by its own count, not by comparing values)
-            history = [list(h)[: int(iters[bi]) + 1] for bi, h in enumerate(res.history_per_model)]
+            # as Spark's objectiveHistory: the start + one entry per step the model took — minimize_wolfe
+            # owns that (it knows which batch iterations a model's search failed in), no second cut here
+            history = res.history_per_model
         elif design.native:
             if ent is not None:
                 solver = ent.solver

@@ -118,8 +118,8 @@ class ForestBuilder:
         from ..ops.stats import bin_features
 
         self.sparse = None
-        if (hybrid is not None and X.is_cuda and T.hybrid_tree_ok(hybrid) and hybrid.n_rows == X.shape[0]
-                and self.max_bins <= 32):
+        if (hybrid is not None and X.is_cuda and hybrid.n_rows == X.shape[0]
+                and T.hybrid_tree_ok(hybrid, self.max_bins, self.K, subset_size(self.subset, X.shape[1], self.T))):
             # one-hot-aware path (ops/tree.py): findSplits sorts the numeric block only (on the device,
             # no host round trip), the bins come from the hybrid parts, the level histograms of the
             # one-hot columns run over their entries
@@ -772,13 +772,14 @@ class _TreeEstimatorBase(Estimator, ClassifierParams):
         K = num_label_classes(table, self.labelCol, dev)
         return X, y, K
 
-    def _hybrid(self, table: Table, device):
+    def _hybrid(self, table: Table, device, num_classes: Optional[int] = None):
         """The column's one-hot index + numeric layout when it has one-hot blocks (the reference
-        encoding) and the one-hot-aware tree path takes it, else None (features.hybrid)."""
+        encoding) and the one-hot-aware tree path takes it for this estimator's maxBins (and
+        ``num_classes``, when given), else None (features.hybrid)."""
         from ..features.hybrid import tree_hybrid
 
         hm = tree_hybrid(table, self.featuresCol, device)
-        return hm if T.hybrid_tree_ok(hm) else None
+        return hm if T.hybrid_tree_ok(hm, self.maxBins, num_classes) else None
 
     def _thresholds(self, X, hybrid):
         if hybrid is not None:
@@ -798,7 +799,7 @@ class DecisionTreeClassifier(_TreeEstimatorBase):
 
     def fit(self, table: Table) -> DecisionTreeClassificationModel:
         X, y, K = self._prep(table)
-        hm = self._hybrid(table, X.device)
+        hm = self._hybrid(table, X.device, K)
         if dp_context() is None:
             return self.fit_tensors(X, y, K, hybrid=hm)
         thr = self._thresholds(X, hm)
@@ -868,7 +869,7 @@ class RandomForestClassifier(_TreeEstimatorBase):
 
     def fit(self, table: Table) -> RandomForestClassificationModel:
         X, y, K = self._prep(table)
-        hm = self._hybrid(table, X.device)
+        hm = self._hybrid(table, X.device, K)
         ctx = dp_context()
         if ctx is None:
             return self.fit_tensors(X, y, K, hybrid=hm)
@@ -891,7 +892,7 @@ class RandomForestClassifier(_TreeEstimatorBase):
         strategy = self.featureSubsetStrategy
         if str(strategy).lower() == "auto":
             strategy = "all" if self.numTrees == 1 else "sqrt"
-        if hybrid is not None and not (X.is_cuda and T.hybrid_tree_ok(hybrid)):
+        if hybrid is not None and not (X.is_cuda and T.hybrid_tree_ok(hybrid, self.maxBins, K)):
             hybrid = None
         if thresholds is None:
             thresholds = self._thresholds(X, hybrid)
@@ -965,7 +966,7 @@ class RandomForestClassifier(_TreeEstimatorBase):
 def _fit_sharded(b: "ForestBuilder", X, y, row_weight, max_bins: int, seed: int, hybrid=None) -> ForestArrays:
     """``b.fit`` over the whole matrix, or — inside ``data_parallel`` — over this rank's
     row shard (thresholds from the whole matrix, so every rank bins identically)."""
-    if hybrid is not None and not (X.is_cuda and T.hybrid_tree_ok(hybrid)):
+    if hybrid is not None and not (X.is_cuda and T.hybrid_tree_ok(hybrid, b.max_bins, b.K)):
         hybrid = None
     if dp_context() is None:
         return b.fit(X, y, row_weight=row_weight, hybrid=hybrid)

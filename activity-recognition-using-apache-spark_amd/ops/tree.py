@@ -227,10 +227,44 @@ def sparse_args(sparse: Optional[SparseTreeInput]):
     return (sparse.cat.data_ptr(), int(sparse.cat.shape[1]), sparse.onehot.data_ptr())
 
 
-def hybrid_tree_ok(hm) -> bool:
-    """A hybrid matrix the one-hot-aware tree path takes: on a GPU, 1..SPARSE_MAX_NCAT one-hot blocks."""
-    return (SPARSE_TREES and hm is not None and hm.device.type == "cuda"
-            and 0 < int(hm.cat.shape[1]) <= SPARSE_MAX_NCAT and hm.n_features <= 32767)
+SPARSE_LDS_CAP = 150 * 1024  # tree.hip: the level kernel's launcher refuses more dynamic LDS (code -3)
+SPARSE_KMAX = 32             # tree.hip KMAX
+
+
+def hist_feature_chunk(m: int, max_bins: int, num_classes: int) -> int:
+    """Features per workgroup of the level histogram kernel: ``m`` sampled features, at most LDS_BUDGET bytes
+    of histogram."""
+    return max(1, min(m, LDS_BUDGET // (max_bins * num_classes * 4)))
+
+
+def sparse_hist_lds_bytes(n_features: int, max_bins: int, num_classes: int, m: Optional[int] = None) -> int:
+    """Dynamic LDS of one one-hot-aware level-kernel workgroup, as ``har_tree_hist_split_planned`` (tree.hip)
+    sizes it: the histogram and slot map of the ``fc`` features of a chunk, then the class totals, the
+    column -> slot map of all ``n_features`` columns and the slots' flags.  ``m``: sampled features per node
+    (default: all)."""
+    fc = hist_feature_chunk(n_features if m is None else m, max_bins, num_classes)
+    return fc * max_bins * num_classes * 4 + fc * 4 + num_classes * 4 + n_features * 2 + fc * 3
+
+
+def hist_float_atomics() -> bool:
+    """tree.hip's A/B switch ``HAR_HIST_FLOAT_ATOMICS=1`` (float histogram atomics), which its one-hot-aware
+    kernel refuses (code -8).  The library reads the variable once, at its first level launch."""
+    return os.environ.get("HAR_HIST_FLOAT_ATOMICS", "")[:1] == "1"
+
+
+def hybrid_tree_ok(hm, max_bins: int = 32, num_classes: Optional[int] = None, m: Optional[int] = None) -> bool:
+    """A hybrid matrix the one-hot-aware tree path takes: on a GPU, 1..SPARSE_MAX_NCAT one-hot blocks, and
+    nothing the level kernel's launcher refuses — 2 <= maxBins <= 32, at most 32,767 columns, a workgroup's LDS
+    (``sparse_hist_lds_bytes`` for the feature chunk the fit will use) within SPARSE_LDS_CAP, integer
+    histogram atomics.  A fit whose matrix is refused here grows the same forest on the dense path.
+    ``num_classes`` None: every class count the kernels take must fit."""
+    if not (SPARSE_TREES and hm is not None and hm.device.type == "cuda"
+            and 0 < int(hm.cat.shape[1]) <= SPARSE_MAX_NCAT and hm.n_features <= 32767):
+        return False
+    if not 2 <= max_bins <= 32 or hist_float_atomics():
+        return False
+    ks = range(2, SPARSE_KMAX + 1) if num_classes is None else (int(num_classes),)
+    return all(sparse_hist_lds_bytes(hm.n_features, max_bins, k, m) <= SPARSE_LDS_CAP for k in ks)
 
 
 def find_thresholds_hybrid(hm, max_bins: int, sample_rows: int = 10000, seed: int = 0, row_offset: int = 0,
@@ -458,7 +492,7 @@ def hist_split_native(bins, nbins_feat, label, rows, row_w, node_start, node_cou
     2^24 — the kernel adds the weights as uint32, so a fractional weight would be truncated."""
     A, m = feats.shape
     F, N = bins.shape
-    fc = max(1, min(m, LDS_BUDGET // (max_bins * K * 4)))
+    fc = hist_feature_chunk(m, max_bins, K)
     chunks = (m + fc - 1) // fc
     dev = bins.device
     gain = torch.empty(A * chunks, dtype=torch.float32, device=dev)
@@ -546,7 +580,7 @@ def hist_split_planned(bins, nbins_feat, label, rows, row_w, node_start, node_co
     below 2^24; the chunk merges and the subtraction are exact only then."""
     A, m = feats.shape
     F, N = bins.shape
-    fc = max(1, min(m, LDS_BUDGET // (max_bins * K * 4)))
+    fc = hist_feature_chunk(m, max_bins, K)
     chunks = (m + fc - 1) // fc
     dev = bins.device
     gain = torch.empty(A * chunks, dtype=torch.float32, device=dev)
@@ -648,7 +682,7 @@ def hist_split_planned_dp(bins, nbins_feat, label, rows, row_w, node_start, node
     rank rows; the owner unpacks its summed row into the fp32 store the split kernel reads."""
     A, m = feats.shape
     F, N = bins.shape
-    fc = max(1, min(m, LDS_BUDGET // (max_bins * K * 4)))
+    fc = hist_feature_chunk(m, max_bins, K)
     chunks = (m + fc - 1) // fc
     dev = bins.device
     exact = a_dev == 0

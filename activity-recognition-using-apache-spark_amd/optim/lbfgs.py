@@ -160,7 +160,9 @@ class TrialResult:
     iterations: torch.Tensor  # [B]
     n_evals: int              # batched evaluations (each covers B x T trial points)
     history: list             # per-iteration mean objective
-    history_per_model: list = None  # [B] lists: each model's own objective per iteration
+    # [B] lists of each model's own objectives.  minimize_trials: one entry per batch iteration (what the
+    # device solver records); minimize_wolfe: the start + one entry per step the model took
+    history_per_model: list = None
 
 
 def _reg_value(x, l2v, l1v):
@@ -367,7 +369,8 @@ def minimize_wolfe(evaluate, x0: torch.Tensor, l2v: torch.Tensor, l1v: Optional[
     failed_once = torch.zeros(B, dtype=torch.bool, device=dev)
     iters = torch.zeros(B, dtype=torch.int64, device=dev)
     head, filled, n_evals = 0, 0, 1
-    fhist = [F.clone()]
+    fhist = [F.clone()]   # one row per batch iteration (the convergence check's memory, the batch mean)
+    takes = []            # ... and which models took a step in it
     rounds_per_iter = []
     for it in range(max_iter):
         pg = pg_fn(x, g)
@@ -506,6 +509,7 @@ def minimize_wolfe(evaluate, x0: torch.Tensor, l2v: torch.Tensor, l1v: Optional[
         F = torch.where(take, F_acc, F)
         iters = iters + take.long()
         fhist.append(F.clone())
+        takes.append(take)
         recent = torch.stack(fhist[-(fval_memory + 1):-1]).max(0).values if len(fhist) > 1 else F
         fconv = (recent - F) / torch.maximum(torch.maximum(F.abs(), recent.abs()), torch.full_like(F, 1e-6)) <= tol
         gconv = pg_fn(x, g).abs().amax(1).double() / dot(x, x).sqrt().clamp_min(1.0) <= tol
@@ -517,7 +521,13 @@ def minimize_wolfe(evaluate, x0: torch.Tensor, l2v: torch.Tensor, l1v: Optional[
         if not bool(active.any()):
             break
     H = torch.stack(fhist).cpu()
+    # a model's own history, as Spark's objectiveHistory: the start objective, then one entry per step it TOOK
+    # (``iterations[b] + 1`` entries).  A batch iteration in which its line search failed, or which ran after
+    # it had stopped, moved nothing and adds no row — cutting the batch rows by the iteration count instead
+    # kept the failed iteration's repeat and dropped the last accepted objectives.
+    took = torch.stack(takes).cpu() if takes else torch.zeros(0, B, dtype=torch.bool)
+    keep = torch.cat([torch.ones(1, B, dtype=torch.bool), took])
     res = TrialResult(x=x, f=F, iterations=iters, n_evals=n_evals, history=H.mean(1).tolist(),
-                      history_per_model=[H[:, b].tolist() for b in range(B)])
+                      history_per_model=[H[keep[:, b], b].tolist() for b in range(B)])
     res.rounds_per_iter = rounds_per_iter
     return res

@@ -32,6 +32,7 @@
 // deviation; resultant = mean sqrt(x^2+y^2+z^2); peak = mean time (ms) between local maxima
 // above mean + 0.5 (max - mean) (NaN — the '?' of the WISDM table — when fewer than two peaks).
 #include <algorithm>
+#include <cfloat>
 #include <type_traits>
 
 #include "common.h"
@@ -48,6 +49,19 @@ constexpr int SLACK = 16;  // floats after it: the t = W neighbour read of the l
 __host__ __device__ constexpr int reg_nrm_floats(int A) { return (2 * (17 * A + 4 * (A / 3)) + 3) & ~3; }
 
 typedef float v4f __attribute__((ext_vector_type(4)));
+
+// The bin scale of a (window, axis), computed once in the per-window prologue of every kernel here: 0 for a
+// flat axis (range == 0: every sample in bin 0), else 10 / range SATURATED at FLT_MAX.  A range below
+// 10 / FLT_MAX (2.94e-38: some normal and every denormal range; the kernels run with fp32 denormals on) makes
+// fl(10 / range) +inf, and (x - lo) * inf is +inf for x > lo and NaN for x == lo — as an unclamped bin a shift
+// of 64 or more into the packed counts.  Saturated, (x - lo) * sc <= range * FLT_MAX < 10 on such an axis: its
+// samples fall into bins floor((x - lo) * FLT_MAX), the minimum into bin 0, the counts sum to W, and the
+// register and the fallback kernels agree.  A finite 10 / range is untouched.  (features/window.py states the
+// rule; tests/test_gpu_window_degenerate.py.)
+__device__ __forceinline__ float bin_scale(float range) {
+  const float sc = (float)NB / range;
+  return range > 0.f ? (sc < FLT_MAX ? sc : FLT_MAX) : 0.f;
+}
 
 // Reductions over one group of LPW = 8 or 16 lanes; every lane ends with the group's result.
 // quad_perm xor-1, quad_perm xor-2, then row_half_mirror (and row_mirror for 16 lanes): after
@@ -224,7 +238,7 @@ __device__ __forceinline__ void window_groups(const float* img0, int64_t w0, int
   for (int c = 0; c < 3; ++c) {
     const float range = mx[c] - mn[c];
     K.m[c] = mean[c]; K.lo[c] = mn[c];
-    K.bsc[c] = range > 0.f ? (float)NB / range : 0.f;  // one reciprocal per axis, not per sample
+    K.bsc[c] = bin_scale(range);  // one reciprocal per axis, not per sample
     K.thr[c] = mean[c] + 0.5f * (mx[c] - mean[c]);
     a.ad[c] = 0.f; a.v2[c] = 0.f; a.h[c] = 0; a.pk[c] = 0;
     a.npk[c] = 0; a.first[c] = 0x7fffffff; a.last[c] = -1;
@@ -469,6 +483,8 @@ __device__ __forceinline__ void flag_step(uint32_t& R, uint32_t& PT, float x, fl
 // conversion never sees a negative), clamped to bin 9.  (The one-fma form x sc + (-lo sc), one VALU less
 // per sample and axis, moved boundary samples of quantized sensor data — WISDM's 2-decimal readings sit
 // exactly on bin edges — off the float64 definition's bins: tests/test_raw.py; rejected)
+// bin_raw is unclamped: sc comes from bin_scale (above), which keeps (x - lo) * sc <= 10 on every axis, an
+// axis whose 10 / range overflows fp32 included — no per-sample min.
 __device__ __forceinline__ uint32_t bin_raw(float x, float sc, float lo) { return (uint32_t)((x - lo) * sc); }
 __device__ __forceinline__ uint32_t bin_of(float x, float sc, float lo) {
   const uint32_t b = (uint32_t)((x - lo) * sc);
@@ -572,7 +588,7 @@ __device__ __forceinline__ void reg_window_batch(const float* span, int64_t w0, 
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     const float range = mx[c] - mn[c];
-    sc[c] = range > 0.f ? (float)NB / range : 0.f;
+    sc[c] = bin_scale(range);
     off[c] = mn[c];  // bin_of's lo
     thr[c] = mean[c] + 0.5f * (mx[c] - mean[c]);
   }

@@ -207,6 +207,59 @@ def int_stream(shape, r0: int = 0, seed: int = None, S: int = None) -> ExactStre
     return ExactStream(buf, r0, S, v, columns(A))
 
 
+DEGENERATE_Q = (2.0 ** -123, 2.0 ** -128, 2.0 ** -130)
+FLT_MAX = float(np.finfo(np.float32).max)
+
+
+def degenerate_stream(shape, q: float, r0: int = 0) -> ExactStream:
+    """``int_stream`` with the second axis of every triad replaced by ``v * q`` (``q`` a power of two,
+    offset 0): every (window, axis) of it has min 0 and max ``10 q``.  The other axes keep the exact stream.
+
+    q = 2^-123: range 10 * 2^-123, bin scale exactly 2^123 — a small but legitimate range;
+    q = 2^-128: range 10 * 2^-128 = 1.25 * 2^-125 (a normal float), ``10 / range`` = 2^128 overflows fp32; the
+                samples ``v q`` are denormal for v <= 3 and normal above;
+    q = 2^-130: the same with every sample (v <= 10 < 16) denormal."""
+    es = int_stream(shape, r0)
+    A = shape[0]
+    x = torch.from_numpy(es.ints.astype(np.float64) * q).float()
+    assert torch.equal(x.double(), torch.from_numpy(es.ints.astype(np.float64) * q)), "v * q must be exact in fp32"
+    buf = es.buf.clone()
+    for a in range(1, A, 3):
+        buf[r0: r0 + es.S, a] = x[:, a]
+    return ExactStream(buf, r0, es.S, es.ints, es.cols)
+
+
+def degenerate_bins_fp32(x: torch.Tensor, W: int, stride: int, scaled: bool = False):
+    """The window kernels' bin arithmetic in plain fp32 torch on the CPU, denormals kept as the kernels keep
+    them (their code objects run with fp32 denormals on): per (window, axis)
+
+        range = max - min
+        sc    = 0                               if range == 0 (a flat axis: every sample in bin 0)
+                min(fl(10 / range), FLT_MAX)    otherwise (the scale saturates where 10 / range overflows)
+        bin   = min(trunc(fl(fl(x - min) * sc)), 9)
+
+    Returns the int64 counts [n_windows, A, 10] (``scaled``: also the products ``(x - min) * sc``)."""
+    assert x.dtype == torch.float32 and not x.is_cuda
+    tiny = torch.tensor([2.0 ** -130], dtype=torch.float32)
+    assert float(tiny * 0.5) == 2.0 ** -131, "this process flushes fp32 denormals: the emulation needs them"
+    w = x.unfold(0, W, stride)                                   # [nw, A, W]
+    lo, hi = w.min(-1).values, w.max(-1).values
+    rng = hi - lo
+    sc = torch.where(rng > 0, (10.0 / rng).clamp_max(FLT_MAX), torch.zeros_like(rng))
+    p = (w - lo[..., None]) * sc[..., None]
+    assert p.dtype == torch.float32
+    counts = torch.nn.functional.one_hot(p.to(torch.int64).clamp_max(9), 10).sum(-2)
+    return (counts, p) if scaled else counts
+
+
+@lru_cache(maxsize=None)
+def degenerate_reference(shape, q: float) -> torch.Tensor:
+    """The float64 oracle's rows of ``degenerate_stream(shape, q)`` (computed once; do not modify)."""
+    from har.features.window import window_features_torch
+
+    return window_features_torch(degenerate_stream(shape, q).view(), shape[1], shape[2], HZ)
+
+
 @lru_cache(maxsize=None)
 def reference(shape) -> torch.Tensor:
     """The float64 oracle's rows for a table row (computed once; do not modify)."""
@@ -220,7 +273,14 @@ def bits(t: torch.Tensor) -> torch.Tensor:
     return t.contiguous().view(torch.int32 if t.dtype == torch.float32 else torch.int16)
 
 
-def check_exact(out: torch.Tensor, ref: torch.Tensor, A: int, W: int) -> None:
+def axis_columns(A: int, name: str, axes) -> list:
+    """Column indices of the per-axis feature ``name`` (10 per axis for "bins", else 1) for the given axes."""
+    s = columns(A)[name]
+    per = (s.stop - s.start) // A
+    return [s.start + a * per + j for a in axes for j in range(per)]
+
+
+def check_exact(out: torch.Tensor, ref: torch.Tensor, A: int, W: int, axes=None) -> None:
     """A kernel's fp32 rows against the float64 oracle's on the exact stream (both on the CPU).
 
     bins       |out W - round(ref W)| <= 1e-3: (x - lo) * sc is an exact integer, no sample may move
@@ -231,25 +291,32 @@ def check_exact(out: torch.Tensor, ref: torch.Tensor, A: int, W: int) -> None:
                products and the reference's rounding: 5 * 2^-24 = 3.0e-7
     absdev, std, resultant, corr   rtol = atol = 2e-4, the tolerance tests/test_window.py uses
     all        no NaN outside the peak columns
-    """
+
+    ``axes``: only the per-axis columns (bins, avg, peak, absdev, std, min, max, energy) of these axes, with
+    the same bounds; the per-triad columns (resultant, corr) are then left out."""
     c = columns(A)
     assert out.shape == ref.shape and out.dtype == torch.float32
+    if axes is None:
+        sel = {name: list(range(s.start, s.stop)) for name, s in c.items()}
+        loose = LOOSE_COLS
+    else:
+        sel = {name: axis_columns(A, name, axes) for name in c if name not in ("resultant", "corr")}
+        loose = ("absdev", "std")
     o, r = out.double(), ref.double()
-    notpeak = torch.ones(out.shape[1], dtype=torch.bool)
-    notpeak[c["peak"]] = False
+    notpeak = sorted(i for name, idx in sel.items() if name != "peak" for i in idx)
     assert not bool(torch.isnan(out[:, notpeak]).any()), "NaN outside the peak columns: a read outside the stream"
-    cnt = o[:, c["bins"]] * W
-    want = torch.round(r[:, c["bins"]] * W)
+    cnt = o[:, sel["bins"]] * W
+    want = torch.round(r[:, sel["bins"]] * W)
     err = (cnt - want).abs()
     assert float(err.max()) <= 1e-3, "bin counts differ: max |out W - count| = %g at %s" % (
         float(err.max()), tuple(int(i) for i in np.unravel_index(int(err.argmax()), err.shape)))
     for name in ("min", "max"):
-        assert torch.equal(bits(out[:, c[name]]), bits(ref[:, c[name]])), name
+        assert torch.equal(bits(out[:, sel[name]]), bits(ref[:, sel[name]])), name
     for name in ("avg", "energy"):
-        torch.testing.assert_close(o[:, c[name]], r[:, c[name]], rtol=2.5e-7, atol=0, msg=lambda m, n=name: n + ": " + m)
-    po, pr = o[:, c["peak"]], r[:, c["peak"]]
+        torch.testing.assert_close(o[:, sel[name]], r[:, sel[name]], rtol=2.5e-7, atol=0, msg=lambda m, n=name: n + ": " + m)
+    po, pr = o[:, sel["peak"]], r[:, sel["peak"]]
     assert torch.equal(torch.isnan(po), torch.isnan(pr)), "peak columns: NaN pattern (fewer than two peaks) differs"
     torch.testing.assert_close(po, pr, rtol=1e-6, atol=0, equal_nan=True, msg=lambda m: "peak: " + m)
-    for name in LOOSE_COLS:
-        torch.testing.assert_close(out[:, c[name]], ref[:, c[name]], rtol=2e-4, atol=2e-4,
+    for name in loose:
+        torch.testing.assert_close(out[:, sel[name]], ref[:, sel[name]], rtol=2e-4, atol=2e-4,
                                    msg=lambda m, n=name: n + ": " + m)

@@ -325,6 +325,60 @@ def test_rccl_forest_node_owner(rccl, cuda, kind):
     assert torch.equal(m.arrs.stats, r.arrs.stats)
 
 
+@pytest.mark.parametrize("kind", ["dt", "rf"])
+def test_rccl_forest_one_hot_aware_path_under_data_parallel(rccl, cuda, kind, monkeypatch):
+    """The one-hot-aware tree path in its data-parallel form, which the estimators take by default inside
+    ``data_parallel``: thresholds from the hybrid matrix, the rank's row shard of it, the level histograms of
+    the one-hot-aware kernel reduce-scattered by node owner and searched from the reduced store.  On the
+    forced group, with the path on and off, and without a group: the same forest bit for bit — and the "on"
+    fit really hands the kernel its one-hot input at every level."""
+    from _tree_sparse_util import dense_path, same_arrays, synthetic_hybrid
+
+    from har.models.tree import DecisionTreeClassifier, RandomForestClassifier
+    from har.ops import tree as T
+    from har.parallel import data_parallel as dp
+
+    hm, y = synthetic_hybrid(cuda, N=6000)
+    X = hm.to_dense()
+    assert T.hybrid_tree_ok(hm, 32, 4)
+
+    def est():
+        return DecisionTreeClassifier(maxDepth=3, seed=3) if kind == "dt" else RandomForestClassifier(
+            numTrees=5, maxDepth=4, seed=5)
+
+    levels = []  # per level call of a fit: did the kernel get the one-hot input?
+    for name in ("hist_split_planned_dp", "hist_split_native", "hist_split_planned"):
+        def spy(*a, _real=getattr(T, name), _name=name, **k):
+            levels.append((_name, k.get("sparse") is not None, k.get("owner") is not None))
+            return _real(*a, **k)
+
+        monkeypatch.setattr(T, name, spy)
+
+    def in_group():
+        # as DecisionTreeClassifier.fit / RandomForestClassifier.fit inside data_parallel (row shard [0, N))
+        e = est()
+        h = hm if T.hybrid_tree_ok(hm, e.maxBins, 4) else None
+        owner = dp.NodeOwner(rccl)
+        assert not owner.solo
+        m = e.fit_tensors(X, y, 4, row_offset=0, thresholds=e._thresholds(X, h), owner=owner,
+                          hybrid=None if h is None else h.rows(0, hm.n_rows))
+        assert owner.stats["reduce_scatter"] >= 1 and owner.stats["all_gather"] >= 1, owner.stats
+        return m
+
+    on = in_group()
+    seen_on, levels[:] = list(levels), []
+    off = dense_path(in_group)
+    seen_off, levels[:] = list(levels), []
+    solo = est().fit_tensors(X, y, 4, hybrid=hm)
+    seen_solo = list(levels)
+    assert len(seen_on) >= 2 and all(s and o and n != "hist_split_planned" for n, s, o in seen_on), seen_on
+    assert len(seen_off) == len(seen_on) and not any(s for _, s, _ in seen_off), seen_off
+    assert seen_solo and all(s and not o for _, s, o in seen_solo), seen_solo
+    same_arrays(on.arrs, off.arrs)
+    same_arrays(on.arrs, solo.arrs)
+    assert int(on.arrs.n_nodes.min()) > 1
+
+
 @pytest.mark.parametrize("graph", ["2", "-1"])
 def test_rccl_bench_graph2_subprocess(cuda, tmp_path, graph):
     """bench.py in its DP form on the forced RCCL group: segmented graphs around the eager RCCL

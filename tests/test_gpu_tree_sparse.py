@@ -8,12 +8,21 @@ hybrid parts and histograms a one-hot column over its nonzeros only (bin 0 = nod
 Every test pins it to the dense path of the same fit: thresholds, bins and whole forests bit for bit.
 """
 import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
 import torch
 
+from _tree_sparse_util import arrays_hash as _arrays_hash
+from _tree_sparse_util import dense_path as _dense_path
+from _tree_sparse_util import same_arrays as _same_arrays
+from _tree_sparse_util import synthetic_hybrid as _synthetic_hybrid
+
 pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -22,47 +31,6 @@ def wisdm_ref(cuda, wisdm_csv):
 
     train, test, _ = load_wisdm(wisdm_csv, "reference", 2018, device=cuda)
     return train, test
-
-
-def _dense_path(fn):
-    from har.ops import tree as T
-
-    old = T.SPARSE_TREES
-    T.SPARSE_TREES = False
-    try:
-        return fn()
-    finally:
-        T.SPARSE_TREES = old
-
-
-def _same_arrays(a, b):
-    for k in ("feature", "threshold", "left", "right", "stats", "gain"):
-        x, y = getattr(a, k), getattr(b, k)
-        assert torch.equal(x, y), k
-    assert np.array_equal(a.n_nodes, b.n_nodes)
-
-
-def _synthetic_hybrid(cuda, N=24000, widths=(40, 7, 3), Fd=5, seed=0, all_ones_block=False):
-    """A hybrid matrix with some one-hot columns absent (no 1 in any row), the last category dropped
-    (-1 rows) and, optionally, a block whose first column is set in every row (no split)."""
-    from har.features.hybrid import HybridMatrix
-
-    g = torch.Generator().manual_seed(seed)
-    blocks, off, cats = [], 0, []
-    for i, w in enumerate(widths):
-        c = torch.randint(-1, w - 2, (N,), generator=g)  # columns w-2, w-1 never set
-        if all_ones_block and i == len(widths) - 1:
-            c = torch.zeros(N, dtype=torch.int64)
-        cats.append(torch.where(c >= 0, c + off, c).to(torch.int32))
-        blocks.append((off, w))
-        off += w
-    dense = torch.randn(N, Fd, generator=g)
-    dense[:, 0] = torch.randint(0, 4, (N,), generator=g).float()  # few distinct values: midpoints
-    dense[::97, 1] = float("nan")
-    dense_cols = torch.arange(off, off + Fd, dtype=torch.int32)
-    hm = HybridMatrix(dense.to(cuda), dense_cols.to(cuda), torch.stack(cats, 1).contiguous().to(cuda), blocks, off + Fd)
-    y = (cats[0] % 3 + (dense[:, 2] > 0).to(torch.int32)).long().clamp_max(3).to(cuda)
-    return hm, y
 
 
 @pytest.mark.parametrize("n,sample", [(3853, False), (24000, True)])
@@ -160,3 +128,117 @@ def test_sparse_tree_cross_validation_equals_dense(wisdm_ref):
         b = _dense_path(cv)
         assert a.avgMetrics == b.avgMetrics
         _same_arrays(a.bestModel.arrs, b.bestModel.arrs)
+
+
+# --- what the level kernel's launcher refuses, the fit takes on the dense path -------------------------------
+def _launcher_lds(F, max_bins, K, m=None):
+    """``har_tree_hist_split_planned``'s dynamic LDS with the one-hot-aware kernel on (tree.hip), restated:
+    fc * maxbins * K * 4 + fc * 4 + K * 4 + F * 2 + fc * 3, fc = min(m, 96 KB / (maxbins K 4)) features."""
+    fc = max(1, min(F if m is None else m, 96 * 1024 // (max_bins * K * 4)))
+    return fc * max_bins * K * 4 + fc * 4 + K * 4 + F * 2 + fc * 3
+
+
+LDS_CAP = 150 * 1024  # the launcher's limit (contract code -3 above it)
+
+
+def _sparse_calls(monkeypatch):
+    """Counts the fits that take the one-hot-aware path (``ForestBuilder.prepare`` builds its kernel input)."""
+    from har.ops import tree as T
+
+    calls = []
+    real = T.sparse_tree_input
+
+    def spy(hm):
+        calls.append(hm.n_features)
+        return real(hm)
+
+    monkeypatch.setattr(T, "sparse_tree_input", spy)
+    return calls
+
+
+def _wide_hybrid(cuda, width):
+    hm, y = _synthetic_hybrid(cuda, N=512, widths=(width,), Fd=5, seed=9)
+    assert hm.n_features == width + 5 and int(y.max()) == 3
+    return hm, y
+
+
+def test_hybrid_too_wide_for_the_sparse_kernels_lds_takes_the_dense_path(cuda, monkeypatch):
+    """One one-hot block of 28,000 columns + 5 numeric ones, K = 4, maxBins = 32: the one-hot-aware kernel
+    would need 192 * 32 * 4 * 4 + 192 * 4 + 4 * 4 + 28,005 * 2 + 192 * 3 = 155,674 bytes of LDS, above the
+    launcher's 153,600.  The fit must not raise: ``hybrid_tree_ok`` refuses the matrix and the depth-3 tree
+    is the dense path's."""
+    from har.models.tree import DecisionTreeClassifier
+    from har.ops import tree as T
+
+    hm, y = _wide_hybrid(cuda, 28000)
+    assert _launcher_lds(hm.n_features, 32, 4) == 155674 > LDS_CAP
+    calls = _sparse_calls(monkeypatch)
+    X = hm.to_dense()
+    m = DecisionTreeClassifier(maxDepth=3).fit_tensors(X, y, 4, hybrid=hm)
+    assert not calls
+    r = _dense_path(lambda: DecisionTreeClassifier(maxDepth=3).fit_tensors(X, y, 4))
+    _same_arrays(m.arrs, r.arrs)
+    assert int(m.arrs.n_nodes[0]) > 1
+    assert T.hybrid_tree_ok(hm, 32, 4) is False and T.hybrid_tree_ok(hm) is False
+    assert T.sparse_hist_lds_bytes(hm.n_features, 32, 4) == 155674
+
+
+def test_widest_hybrid_the_sparse_kernel_takes_equals_dense(cuda, monkeypatch):
+    """The largest column count the launcher's LDS formula accepts at K = 4, maxBins = 32 (and one more is
+    refused): ``hybrid_tree_ok`` agrees on both sides of the limit, the accepted matrix really takes the
+    one-hot-aware kernel, and its tree is the dense path's bit for bit."""
+    from har.models.tree import DecisionTreeClassifier
+    from har.ops import tree as T
+
+    F = max(f for f in range(6, 32768) if _launcher_lds(f, 32, 4) <= LDS_CAP)
+    assert _launcher_lds(F + 1, 32, 4) > LDS_CAP and 20000 < F < 28005
+    hm, y = _wide_hybrid(cuda, F - 5)
+    over, _ = _wide_hybrid(cuda, F - 4)
+    assert T.hybrid_tree_ok(hm, 32, 4) is True and T.hybrid_tree_ok(over, 32, 4) is False
+    calls = _sparse_calls(monkeypatch)
+    X = hm.to_dense()
+    m = DecisionTreeClassifier(maxDepth=3).fit_tensors(X, y, 4, hybrid=hm)
+    assert calls == [F]
+    r = _dense_path(lambda: DecisionTreeClassifier(maxDepth=3).fit_tensors(X, y, 4))
+    assert calls == [F]
+    _same_arrays(m.arrs, r.arrs)
+    assert int(m.arrs.n_nodes[0]) > 1
+
+
+_FLOAT_ATOMICS_CHILD = """
+import sys
+sys.path.insert(0, "tests")
+import torch
+from _tree_sparse_util import arrays_hash, synthetic_hybrid
+from har.models.tree import DecisionTreeClassifier
+from har.ops import tree as T
+
+cuda = torch.device("cuda:0")
+hm, y = synthetic_hybrid(cuda, N=2000)
+m = DecisionTreeClassifier(maxDepth=3).fit_tensors(hm.to_dense(), y, 4, hybrid=hm)
+print("OK", int(T.hybrid_tree_ok(hm, 32, 4)), int(T.hybrid_tree_ok(hm)), arrays_hash(m.arrs))
+"""
+
+
+def test_float_atomics_switch_takes_the_dense_path(cuda):
+    """``HAR_HIST_FLOAT_ATOMICS=1`` (read once per process by the library, hence a fresh child): the launcher
+    refuses the one-hot-aware kernel (code -8), so ``hybrid_tree_ok`` must too and the fit must grow the dense
+    path's tree — which, the float and the integer histograms being equal on integer weights, is this
+    process's dense-path tree."""
+    from har.models.tree import DecisionTreeClassifier
+    from har.ops import tree as T
+
+    assert os.environ.get("HAR_HIST_FLOAT_ATOMICS", "0")[:1] != "1"
+    hm, y = _synthetic_hybrid(cuda, N=2000)
+    assert T.hybrid_tree_ok(hm, 32, 4)
+    X = hm.to_dense()
+    want = _arrays_hash(_dense_path(lambda: DecisionTreeClassifier(maxDepth=3).fit_tensors(X, y, 4)).arrs)
+    assert want == _arrays_hash(DecisionTreeClassifier(maxDepth=3).fit_tensors(X, y, 4, hybrid=hm).arrs)
+    env = dict(os.environ, HAR_HIST_FLOAT_ATOMICS="1")
+    env.pop("HAR_TREE_SPARSE", None)
+    r = subprocess.run([sys.executable, "-c", _FLOAT_ATOMICS_CHILD], cwd=ROOT, env=env, capture_output=True,
+                       text=True, timeout=240)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = [ln for ln in r.stdout.splitlines() if ln.startswith("OK ")][-1].split()
+    assert line[1:3] == ["0", "0"], line
+    assert line[3] == want

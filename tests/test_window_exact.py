@@ -1,7 +1,10 @@
 """Preconditions of the exact-count window tests (tests/test_gpu_window_exact.py), on the CPU: the stream of
 ``_window_util.int_stream`` really has the properties that let the GPU test demand exact bin counts, exact
 peak sets and bit-equal extrema from the kernels, and the dispatch table it runs matches the launcher's rules.
-If a seed violates one of these, change the seed (``_window_util.seed_of``), never a bound."""
+If a seed violates one of these, change the seed (``_window_util.seed_of``), never a bound.
+
+Also the preconditions of tests/test_gpu_window_degenerate.py: the streams with an axis whose bin scale
+``10 / range`` is huge or overflows fp32, and the fp32 emulation of the kernels' documented rule for them."""
 import numpy as np
 import pytest
 import torch
@@ -143,6 +146,113 @@ def _preconditions(shape, x, v, ref):
         t = torch.arange(1, W - 1)
         assert int((pk & plateau & (t % C == C - 1)).sum()) > 0, "no plateau peak closes a lane's run"
         assert int((pk & (t % C == 0)).sum()) > 0, "no peak opens a lane's run"
+
+
+def _degenerate(shape, q):
+    """The degenerate stream of a row, its emulated counts / scaled samples and the integer draws per window."""
+    A, W, stride = shape[:3]
+    es = U.degenerate_stream(shape, q)
+    counts, p = U.degenerate_bins_fp32(es.view(), W, stride, scaled=True)
+    v = torch.from_numpy(es.ints.copy()).unfold(0, W, stride)
+    assert counts.shape == (U.n_windows(shape), A, 10) and p.shape == v.shape
+    return es, counts, p, v
+
+
+@pytest.mark.parametrize("shape", U.SHAPES, ids=U.shape_id)
+def test_degenerate_stream_is_the_exact_stream_with_a_tiny_second_axis(shape):
+    A, W, stride = shape[:3]
+    base = U.int_stream(shape)
+    for q in U.DEGENERATE_Q:
+        es = U.degenerate_stream(shape, q, 1)
+        x = es.view()
+        assert torch.equal(es.view(), U.degenerate_stream(shape, q).view()) and es.S == base.S
+        assert bool(torch.isnan(es.buf[:1]).all()) and bool(torch.isnan(es.buf[1 + es.S:]).all())
+        for a in range(A):
+            if a % 3 != 1:
+                assert torch.equal(x[:, a], base.view()[:, a])
+                continue
+            assert np.array_equal(x[:, a].double().numpy(), es.ints[:, a] * q)   # v * q, exact
+            w = x[:, a].unfold(0, W, stride)
+            assert bool((w.min(-1).values == 0).all()) and bool((w.max(-1).values == np.float32(10 * q)).all())
+        # the three regimes: a finite scale of exactly 2^123; an overflowing one over a normal range with
+        # normal and denormal samples; the same with every sample denormal
+        rng = torch.tensor(10 * q, dtype=torch.float32)
+        tiny = float(np.finfo(np.float32).tiny)
+        if q == 2.0 ** -123:
+            assert float(10.0 / rng) == 2.0 ** 123
+        else:
+            assert bool(torch.isinf(10.0 / rng)) and float(rng) > 0
+            pos = x[:, 1][x[:, 1] > 0]
+            assert bool((pos < tiny).all()) == (q == 2.0 ** -130)
+            if W >= 33:  # (shorter windows hold little beside the planted 0 and 10)
+                assert bool((pos < tiny).any())
+            assert (float(rng) >= tiny) == (q == 2.0 ** -128)
+
+
+@pytest.mark.parametrize("shape", U.SHAPES, ids=U.shape_id)
+def test_degenerate_emulation_equals_the_oracle_where_the_scale_is_finite(shape):
+    """q = 2^-123: ``10 / range`` is exactly 2^123 and ``(x - lo) * sc`` the integer draw, so the fp32 rule
+    must give the float64 oracle's bins on every axis — the saturation touches no legitimate small range."""
+    A, W = shape[:2]
+    q = 2.0 ** -123
+    es, counts, p, v = _degenerate(shape, q)
+    ref = U.degenerate_reference(shape, q).double()
+    want = torch.round(ref[:, es.cols["bins"]] * W).long().view(-1, A, 10)
+    assert torch.equal(counts, want)
+    assert torch.equal(p.double(), v.double())
+    assert torch.equal(counts, torch.nn.functional.one_hot(v.clamp(max=9), 10).sum(-2))
+
+
+@pytest.mark.parametrize("q", U.DEGENERATE_Q[1:], ids=["2^-128", "2^-130"])
+@pytest.mark.parametrize("shape", U.SHAPES, ids=U.shape_id)
+def test_degenerate_emulation_counts_where_the_scale_overflows(shape, q):
+    """``10 / range`` = +inf: with the scale saturated at FLT_MAX the ten counts of such an axis are integers
+    >= 0 that sum to W, every sample equal to the window's minimum lies in bin 0, and ``(x - lo) * sc`` stays
+    below 11 (here: below 10, since range * FLT_MAX < 10 wherever 10 / range overflows).  In closed form
+    ``v q * FLT_MAX`` is ``v (1 - 2^-24)`` at q = 2^-128 (bin v - 1, draw 0 in bin 0) and a quarter of that at
+    q = 2^-130 (bin ceil(v / 4) - 1).  The other axes keep the oracle's bins."""
+    A, W = shape[:2]
+    es, counts, p, v = _degenerate(shape, q)
+    assert counts.dtype == torch.int64 and bool((counts >= 0).all()) and bool((counts.sum(-1) == W).all())
+    ref = U.degenerate_reference(shape, q).double()
+    want = torch.round(ref[:, es.cols["bins"]] * W).long().view(-1, A, 10)
+    for a in range(A):
+        if a % 3 != 1:
+            assert torch.equal(counts[:, a], want[:, a])
+            continue
+        pa, va = p[:, a], v[:, a]
+        assert bool(torch.isfinite(pa).all()) and float(pa.max()) < 11 and float(pa.max()) < 10 and float(pa.min()) == 0
+        assert bool((pa[va == 0] == 0).all()) and int(counts[:, a, 0].min()) >= 1
+        assert bool((counts[:, a, 0] >= (va == 0).sum(-1)).all())
+        b = (va - 1).clamp(min=0) if q == 2.0 ** -128 else ((va + 3) // 4 - 1).clamp(min=0)
+        assert torch.equal(counts[:, a], torch.nn.functional.one_hot(b, 10).sum(-2))
+        assert not torch.equal(counts[:, a], want[:, a])   # (the float64 definition's bins: not the fp32 rule's)
+
+
+def test_check_exact_on_an_axis_subset():
+    """``check_exact(axes=...)`` takes the per-axis columns of those axes only: an edit of another axis or of
+    a per-triad column passes, the same edits as below on a chosen axis do not."""
+    shape = U.SHAPES[2]
+    A, W = shape[0], shape[1]
+    ref = U.reference(shape)
+    c = U.columns(A)
+    keep = [a for a in range(A) if a % 3 != 1]
+    assert U.axis_columns(A, "bins", [1]) == list(range(10, 20)) and U.axis_columns(A, "max", [0, 5]) == [
+        c["max"].start, c["max"].start + 5]
+    out = ref.clone()
+    out[:, U.axis_columns(A, "bins", [1, 4])] = 7.0
+    out[:, U.axis_columns(A, "std", [4])] = float("nan")
+    out[:, c["corr"]] = float("nan")
+    out[:, c["resultant"]] = -1.0
+    U.check_exact(out, ref, A, W, axes=keep)
+    with pytest.raises(AssertionError):
+        U.check_exact(out, ref, A, W)
+    for name, a in (("bins", 0), ("bins", 5), ("min", 2), ("energy", 3), ("std", 0), ("peak", 5)):
+        bad = ref.clone()
+        col = U.axis_columns(A, name, [a])[0]
+        bad[3, col] = float("nan") if name == "peak" else bad[3, col] + 1.0 / W
+        with pytest.raises(AssertionError):
+            U.check_exact(bad, ref, A, W, axes=keep)
 
 
 def test_check_exact_rejects_one_moved_sample():

@@ -110,6 +110,110 @@ def test_wolfe_batch_equals_single_model_solves():
         assert rs.history_per_model[0] == rb.history_per_model[b][:n]
 
 
+MAX_ZOOM = 10  # minimize_wolfe's default zoom budget
+
+
+class _FailOneSearch:
+    """``evaluate`` with one sabotaged line search: from batched evaluation ``first_call`` on (0 = the initial
+    one), for ``1 + MAX_ZOOM`` calls, model 0's loss is 10 above the true one — above phi(0) at every trial
+    point, so its strong-Wolfe search goes bracket -> zoom and spends the zoom budget (one bracketing trial,
+    ``MAX_ZOOM`` zoom trials) and fails.  The gradient and every other model are untouched; afterwards the
+    wrapper is the plain callable."""
+
+    def __init__(self, evaluate, first_call):
+        self.evaluate, self.first, self.calls = evaluate, first_call, 0
+
+    def __call__(self, x):
+        loss, G = self.evaluate(x)
+        if self.first <= self.calls < self.first + 1 + MAX_ZOOM:
+            loss = loss.clone()
+            loss[0] += 10.0
+        self.calls += 1
+        return loss, G
+
+
+def _first_call_of_iteration(rounds_per_iter, k):
+    """Index of the batched evaluation that is the first trial of batch iteration ``k``."""
+    return 1 + sum(rounds_per_iter[:k])
+
+
+def _check_history_is_the_path(h, iterations):
+    assert len(h) == iterations + 1, (len(h), iterations)
+    assert all(a != b for a, b in zip(h, h[1:])), h    # no value twice in a row: no row of a failed search
+
+
+def test_wolfe_history_skips_a_failed_line_search():
+    """A model whose line search fails once (history reset, retry from steepest descent) and then goes on:
+    its ``history_per_model`` is the start objective plus one entry per step it TOOK — the failed batch
+    iteration, which moves nothing, adds no row — while the other model of the batch is untouched."""
+    data = _problem(3)
+    l2v, l1v = _reg([0.05, 0.02], [0.0, 0.03])
+    x0 = torch.zeros(2, K * (F + 1))
+    kw = dict(max_iter=12, tol=1e-12, max_zoom=MAX_ZOOM)
+    clean = minimize_wolfe(data, x0, l2v, l1v, **kw)
+    assert clean.iterations.tolist() == [12, 12]
+    k = 2  # the third batch iteration fails for model 0
+    wrapped = _FailOneSearch(data, _first_call_of_iteration(clean.rounds_per_iter, k))
+    trace = []
+    r = minimize_wolfe(wrapped, x0, l2v, l1v, trace=trace, **kw)
+    assert wrapped.calls > wrapped.first + 1 + MAX_ZOOM
+    assert r.rounds_per_iter[:k] == clean.rounds_per_iter[:k] and r.rounds_per_iter[k] >= 1 + MAX_ZOOM
+    # model 0 lost exactly that iteration, recovered, and went on
+    assert r.iterations.tolist() == [11, 12] and int(r.iterations[0]) >= 3
+    h = r.history_per_model[0]
+    steps = [s for s in trace if s["model"] == 0]
+    assert len(steps) == int(r.iterations[0])
+    for i, s in enumerate(steps):
+        assert s["iter"] == i
+        assert h[i] == s["f0"] and h[i + 1] == s["ft"], (i, h[i], s["f0"], h[i + 1], s["ft"])
+    _check_history_is_the_path(h, int(r.iterations[0]))
+    assert h[:k + 1] == clean.history_per_model[0][:k + 1]          # the same path up to the failure
+    assert all(b <= a for a, b in zip(h, h[1:])) and h[-1] == float(r.f[0])
+    # model 1: bit-equal to the unwrapped solve
+    assert r.history_per_model[1] == clean.history_per_model[1]
+    assert torch.equal(r.x[1], clean.x[1]) and float(r.f[1]) == float(clean.f[1])
+    _check_history_is_the_path(r.history_per_model[1], 12)
+    assert len(r.history) == 13  # (the batch mean keeps one row per batch iteration)
+
+
+def test_logistic_regression_wolfe_history_after_a_failed_search(monkeypatch):
+    """``LogisticRegression(lineSearch="wolfe")`` through the same wrapper: the summaries' objectiveHistory is
+    ``minimize_wolfe``'s ``history_per_model`` of that run — one owner of the history, no second cut."""
+    from har.models import logreg as lr_mod
+    from har.models.logreg import FitSpec, LogisticRegression
+
+    g = torch.Generator().manual_seed(4)
+    mu = torch.randn(K, F, generator=g)
+    y = torch.randint(0, K, (N,), generator=g)
+    X = mu[y] + 1.5 * torch.randn(N, F, generator=g)
+    specs = [FitSpec(None, 0.05, 0.0), FitSpec(None, 0.02, 0.0)]
+    est = lambda: LogisticRegression(maxIter=10, tol=1e-12, lineSearch="wolfe")  # noqa: E731
+    clean = est().fit_many(X, y, specs, K)
+    rounds = clean[0].summary["lineSearchRounds"]
+    assert [m.summary["iterations"] for m in clean] == [10, 10]
+    real = lr_mod.lbfgs.minimize_wolfe
+    seen = {}
+
+    def shim(evaluate, *a, **kw):
+        seen["wrapper"] = w = _FailOneSearch(evaluate, _first_call_of_iteration(rounds, 2))
+        seen["res"] = res = real(w, *a, **kw)
+        return res
+
+    monkeypatch.setattr(lr_mod.lbfgs, "minimize_wolfe", shim)
+    ms = est().fit_many(X, y, specs, K)
+    res = seen["res"]
+    assert seen["wrapper"].calls > seen["wrapper"].first + 1 + MAX_ZOOM
+    assert res.iterations.tolist() == [9, 10]
+    for b, m in enumerate(ms):
+        h = m.summary["objectiveHistory"]
+        assert h == res.history_per_model[b]
+        assert m.summary["iterations"] == int(res.iterations[b])
+        _check_history_is_the_path(h, m.summary["iterations"])
+        assert h[-1] == m.summary["objective"]
+    assert ms[1].summary["objectiveHistory"] == clean[1].summary["objectiveHistory"]
+    assert torch.equal(ms[1].coefficientMatrix, clean[1].coefficientMatrix)
+
+
 def test_logistic_regression_wolfe_on_wisdm(wisdm_csv):
     """The reference's LR (maxIter 20, regParam 0.3) and an OWL-QN grid point with lineSearch="wolfe":
     accuracy at least the reference's (0.6148, result.txt:167), one objectiveHistory entry per
