@@ -43,6 +43,11 @@ class RunConfig:
     overlap: float = 0.0                   # fraction of a window shared with the next one
     # RocketFeaturizer (new, opt-in, needs --raw): --rocket N appends ~N MiniRocket-style RKT* columns
     rocket: int = 0
+    # StreamFilter (new, opt-in, needs --raw): Butterworth conditioning of the samples before they are windowed
+    filter: str = ""                       # lowpass | gravity | body
+    filter_cutoff: float = 0.0             # Hz; 0 = the kind's default (hz / 4 for lowpass, 0.3 for gravity / body)
+    filter_order: int = 3
+    filter_zero_phase: bool = False        # forwards and backwards over every (user, activity) run
     # LogisticRegression (main.py:115)
     lr_max_iter: int = 20
     lr_reg: float = 0.3
@@ -180,6 +185,13 @@ def config_from_args(argv=None) -> RunConfig:
             setattr(cfg, f.name, v)
     if cfg.rocket < 0 or (cfg.rocket > 0 and not cfg.raw):
         ap.error("--rocket N (and the rocket preset) featurize a raw stream: give --raw PATH and N > 0")
+    filter_given = cfg.filter or cfg.filter_cutoff != 0.0 or cfg.filter_order != 3 or cfg.filter_zero_phase
+    if filter_given and not cfg.raw:
+        ap.error("--filter (and --filter-cutoff / --filter-order / --filter-zero-phase) condition a raw stream: give --raw PATH")
+    if filter_given and cfg.filter not in ("lowpass", "gravity", "body"):
+        ap.error(f"--filter takes lowpass, gravity or body, got {cfg.filter!r}")
+    if cfg.filter and (not 1 <= cfg.filter_order <= 4 or cfg.filter_cutoff < 0.0 or cfg.filter_cutoff >= cfg.hz / 2):
+        ap.error("--filter-order takes 1..4 and --filter-cutoff a frequency below hz / 2")
     if "rocket" in cfg.encoding and cfg.rocket == 0:
         ap.error(f"--encoding {cfg.encoding} needs --rocket N")
     if (cfg.encoding == "raw" or "dtw" in cfg.classifiers) and not cfg.raw:

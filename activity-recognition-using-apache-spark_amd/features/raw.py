@@ -73,17 +73,26 @@ def read_raw(path: str):
     return c[0].data.astype(np.int64)[ok], act[ok], c[2].data.astype(np.int64)[ok], xyz[ok]
 
 
+def run_offsets(user: np.ndarray, activity: np.ndarray) -> np.ndarray:
+    """int64 [runs + 1]: the first sample of every maximal run of one (user, activity) in file order, then the
+    sample count (``[0]`` for an empty stream) — the segments of ``window_starts`` and of a stream filter."""
+    n = len(user)
+    if n == 0:
+        return np.zeros(1, np.int64)
+    _, acode = np.unique(activity.astype(str), return_inverse=True)
+    change = np.ones(n, dtype=bool)
+    change[1:] = (user[1:] != user[:-1]) | (acode[1:] != acode[:-1])
+    return np.append(np.nonzero(change)[0], n).astype(np.int64)
+
+
 def window_starts(user: np.ndarray, activity: np.ndarray, window: int, stride: int) -> Tuple[np.ndarray, np.ndarray]:
     """(start sample of every window, index of its segment's first sample); windows stay inside
     maximal runs of one (user, activity)."""
     n = len(user)
     if n == 0:
         return np.zeros(0, np.int64), np.zeros(0, np.int64)
-    _, acode = np.unique(activity.astype(str), return_inverse=True)
-    change = np.ones(n, dtype=bool)
-    change[1:] = (user[1:] != user[:-1]) | (acode[1:] != acode[:-1])
-    seg_lo = np.nonzero(change)[0]
-    seg_hi = np.append(seg_lo[1:], n)
+    off = run_offsets(user, activity)
+    seg_lo, seg_hi = off[:-1], off[1:]
     nwin = np.where(seg_hi - seg_lo >= window, (seg_hi - seg_lo - window) // stride + 1, 0)
     seg_of = np.repeat(np.arange(len(seg_lo)), nwin)
     k = np.arange(int(nwin.sum())) - np.repeat(np.cumsum(nwin) - nwin, nwin)
@@ -149,7 +158,7 @@ def _featurize_dp(ctx, xyz_host: np.ndarray, starts: np.ndarray, window: int, hz
 
 
 def raw_to_table(path: str, hz: float = 20.0, window_sec: float = 10.0, overlap: float = 0.0, device=None,
-                 ctx=None, rocket=None, samples: bool = False) -> Table:
+                 ctx=None, rocket=None, samples: bool = False, filter=None) -> Table:
     """Raw rows -> the WISDM transformed table (one row per window, columns of ``wisdm_data.csv:1``).
 
     ``rocket``: a feature count (a ``RocketModel`` is fitted on all windows of the file, see ``fit_rocket``) or
@@ -157,8 +166,24 @@ def raw_to_table(path: str, hz: float = 20.0, window_sec: float = 10.0, overlap:
     the table's ``rocket_model`` attribute.  ``None``: the table is exactly the WISDM one.
 
     ``samples``: append the samples of every window as ``RAW{i}_{X,Y,Z}`` double columns, time-major (sample i
-    axis a is column ``3 i + a`` of them: the flattened window of ``ops/dtw.py``)."""
+    axis a is column ``3 i + a`` of them: the flattened window of ``ops/dtw.py``).
+
+    ``filter``: a 3-axis ``features.filter.StreamFilter`` (``lowpass``, ``gravity``, ``body``, ``sos``) applied to
+    the samples before the windows are placed, every (user, activity) run on its own; everything downstream —
+    features, rocket columns, sample columns — then sees the filtered stream.  Under data parallelism every rank
+    filters the whole stream before it is sharded.  The filtered samples come back to the host once (the rocket
+    fit, the sample columns and the rank shards are cut from the host array) and are uploaded again for the
+    featurizer: fine for a file that was parsed on the host anyway, a round trip a device-resident stream should
+    avoid by calling ``StreamFilter.transform`` and the window kernels on the device tensor directly.  With
+    ``device=None`` (or a CPU device) the filter is the per-sample PyTorch definition: exact, and slow on long runs."""
     user, act, ts, xyz = read_raw(path)
+    if filter is not None:
+        if filter.out_axes(len(AXES)) != len(AXES):
+            raise ValueError(f"the WISDM table has three axes: a {filter.kind!r} filter does not fit (use lowpass, "
+                             "gravity, body or sos)")
+        fdev = torch.device(device) if device is not None else torch.device("cpu")
+        if len(xyz):
+            xyz = filter.transform(torch.as_tensor(xyz).to(fdev), torch.as_tensor(run_offsets(user, act))).cpu().numpy()
     window = int(round(hz * window_sec))
     stride = max(1, int(round(window * (1.0 - overlap))))
     if window < 3:

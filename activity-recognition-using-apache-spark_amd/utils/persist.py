@@ -170,6 +170,10 @@ def _build(md, t, children, device):
         from ..features.rocket import RocketModel
 
         return RocketModel.from_state(t, st, p, uid=uid)
+    if cls == "StreamFilter":
+        from ..features.filter import StreamFilter
+
+        return StreamFilter.from_state(t, p, uid=uid, state=st)
     if cls == "HMMSmootherModel":
         from ..models.hmm import HMMSmootherModel
 

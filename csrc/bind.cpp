@@ -660,6 +660,45 @@ PYBIND11_MODULE(_har_native, m) {
           "hmm_forward_backward");
   });
 
+  // IIR stream filters (sosfilt.hip)
+  m.def("sosfilt_chunk_len", []() { return har_sosfilt_chunk_len(); });
+  m.def("sosfilt_scan_group", []() { return har_sosfilt_scan_group(); });
+  m.def("sosfilt_levels", [](int64_t S, int L, int G) { return har_sosfilt_levels(S, L, G); });
+  m.def("sosfilt_workspace_bytes", [](int64_t S, int A, int ns, int L, int G) {
+    return har_sosfilt_workspace_bytes(S, A, ns, L, G);
+  });
+  m.def("sosfilt", [](u x, u xc, u y, u seg, int64_t n, int64_t nseg, int A, int ns, int L, int G, int reverse,
+                      int init_step, int mode, std::vector<double> sos, std::vector<double> zi, u powers, int levels, u ws,
+                      int64_t ws_bytes, int phase_lo, int phase_hi, u st) {
+    if (ns < 1 || ns > 4 || sos.size() != (size_t)ns * 5 || zi.size() != (size_t)ns * 2)
+      throw std::runtime_error("sosfilt: sos must hold 5 and zi 2 values per section, 1..4 sections");
+    SosFilterArgs a{};
+    a.x = P<const float>(x);
+    a.xc = P<const float>(xc);
+    a.y = P<float>(y);
+    a.seg = P<const int64_t>(seg);
+    a.n_samples = n;
+    a.n_seg = nseg;
+    a.axes = A;
+    a.sections = ns;
+    a.L = L;
+    a.G = G;
+    a.reverse = reverse;
+    a.init_step = init_step;
+    a.mode = mode;
+    for (int j = 0; j < ns; ++j) {
+      for (int i = 0; i < 5; ++i) a.sos[j][i] = sos[j * 5 + i];
+      for (int i = 0; i < 2; ++i) a.zi[j][i] = zi[j * 2 + i];
+    }
+    a.powers = P<const double>(powers);
+    a.levels = levels;
+    a.ws = P<void>(ws);
+    a.ws_bytes = ws_bytes;
+    a.phase_lo = phase_lo;
+    a.phase_hi = phase_hi;
+    check(har_sosfilt(&a, S(st)), "sosfilt");
+  });
+
   // K-means and the silhouette (kmeans.hip)
   m.def("kmeans_rows_per_block", []() { return har_kmeans_rows_per_block(); });
   m.def("kmeans_max_k", []() { return har_kmeans_max_k(); });

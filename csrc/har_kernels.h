@@ -549,6 +549,41 @@ int har_hmm_forward_backward(const double* B, const double* P, const double* p0,
                              int K, int64_t S, int L, void* ws, int64_t ws_bytes, double* gamma, double* loglik,
                              double* xi, int phase_lo, int phase_hi, int variant, hipStream_t s);
 
+// ---- IIR stream filters (sosfilt.hip): cascaded second-order sections as a chunked scan over samples ----
+// x [S][A] fp32 -> y: mode 0 the filtered stream [S][A], 1 [x - y | y] as [S][2A], 2 x - y [S][A] (xc, nullable,
+// replaces x in the complement); every axis on its own, direct form II transposed in fp64, rounded once to fp32
+// (har/ops/sosfilt.py).  sos[j] = (b0, b1, b2, a1, a2) of section j, zi[j] = its (s1, s2) per unit step input.
+// seg [n_seg + 1] int64 on the device (0 first, S last, strictly increasing: validated by the caller on the host;
+// unread when n_seg == 1): the state restarts at every segment start, from zi * x[start] (init_step) or zero.
+// reverse runs every segment from its last sample to its first.  L = samples per chunk, G = elements per group of
+// the carry scan, levels = har_sosfilt_levels(S, L, G); powers [levels][G][2 sections][2 sections] fp64 on the
+// device, entry (l, k) = (M^(L G^l))^(k + 1) for the cascade's transition matrix M.  ws =
+// har_sosfilt_workspace_bytes(...) bytes of device scratch (-1 = bad shape).  Phases phase_lo..phase_hi of 0..2
+// run (0 chunk states, 1 carry scan, 2 apply).  S = 0 launches nothing.  Contract codes: -2 bad shape (A outside
+// 1..9, sections outside 1..4, S >= 2^31 - 256, L outside 1..256, G outside 2..64, levels, mode, workspace too
+// small), -4 null pointer.
+typedef struct SosFilterArgs {
+  const float* x;
+  const float* xc;
+  float* y;
+  const int64_t* seg;
+  int64_t n_samples, n_seg;
+  int axes, sections, L, G;
+  int reverse, init_step, mode;
+  double sos[4][5];
+  double zi[4][2];
+  const double* powers;
+  int levels;
+  void* ws;
+  int64_t ws_bytes;
+  int phase_lo, phase_hi;
+} SosFilterArgs;
+int har_sosfilt_chunk_len();
+int har_sosfilt_scan_group();
+int har_sosfilt_levels(int64_t n_samples, int L, int G);
+int64_t har_sosfilt_workspace_bytes(int64_t n_samples, int axes, int sections, int L, int G);
+int har_sosfilt(const SosFilterArgs* a, hipStream_t s);
+
 // ---- K-means and the silhouette (kmeans.hip): rows x centres on the fp32 matrix cores ----
 // Working rows X [N][D] fp32 (centred by the caller), operand rows C [K][D] with h [K]: the score is
 // s[n][k] = h[k] - <X[n], C[k]> (assignment: C = centres, h = ||C||^2 / 2; silhouette: C = cluster means,

@@ -23,6 +23,7 @@ DecisionTree(+CV), RandomForest(+CV) — plus NaiveBayes and an MLP — and writ
     python main.py --raw raw.csv --preset rocket --save-models models/    # + MiniRocket-style RKT* columns under LR (models/rocket)
     python main.py --raw raw.csv --preset rocket-ridge --ridge-folds 5    # the same columns under RidgeClassifier (CV-chosen penalty)
     python main.py --raw raw.csv --preset dtw --dtw-group-col USER        # nearest neighbours between raw windows under banded DTW
+    python main.py --raw raw.csv --filter body --filter-cutoff 0.3 --save-models models/   # Butterworth-conditioned samples (models/filter)
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 main.py   # data parallel over 8 GPUs (RCCL)
 
 Under ``torch.distributed.run`` every rank loads the (small) table and every model is
@@ -179,14 +180,23 @@ def run(cfg: RunConfig, ctx=None) -> dict:
     timer = PhaseTimer(dev)
 
     log.print("Loading Data Set...")
+    stream_filter = None
     with timer.phase("load_csv"):
         if cfg.raw:  # raw sensor rows -> device windowing + featurization -> the WISDM table
             from har.features.raw import raw_to_table
 
+            if cfg.filter:
+                from har.features.filter import StreamFilter
+
+                stream_filter = StreamFilter(cfg.hz, cfg.filter, cfg.filter_cutoff or None, cfg.filter_order,
+                                             cfg.filter_zero_phase)
+                stream_filter.window_settings = {"hz": cfg.hz, "window_sec": cfg.window_sec, "overlap": cfg.overlap}
             raw = raw_to_table(cfg.raw, hz=cfg.hz, window_sec=cfg.window_sec, overlap=cfg.overlap, device=dev,
-                               ctx=ctx, rocket=cfg.rocket or None, samples=cfg.encoding == "raw")
+                               ctx=ctx, rocket=cfg.rocket or None, samples=cfg.encoding == "raw", filter=stream_filter)
             log.print(f"Raw stream {cfg.raw}: {raw.count()} windows of {int(round(cfg.hz * cfg.window_sec))} "
                       f"samples ({cfg.window_sec:g} s at {cfg.hz:g} Hz, overlap {cfg.overlap:g})")
+            if stream_filter is not None:
+                log.print(f"Samples conditioned by {stream_filter}")
         else:
             raw = read_csv(cfg.data, device=dev if (cfg.csv_device and dev.type == "cuda") else None)
     # the HMM smoother's sequence keys, taken before the feature pipeline prunes the column
@@ -392,6 +402,8 @@ def run(cfg: RunConfig, ctx=None) -> dict:
         persist.save(pipe_model, os.path.join(cfg.save_models, "pipeline"), labels=vocab)
         if getattr(raw, "rocket_model", None) is not None:  # predict.py --raw featurizes with the same transform
             persist.save(raw.rocket_model, os.path.join(cfg.save_models, "rocket"))
+        if stream_filter is not None:  # predict.py --raw conditions the samples with the same sections
+            persist.save(stream_filter, os.path.join(cfg.save_models, "filter"))
         if smoother is not None:
             persist.save(smoother, os.path.join(cfg.save_models, "hmm"), labels=vocab)
     world = ctx.world_size if ctx is not None else 1

@@ -84,17 +84,24 @@ def run(args) -> dict:
         from har.features.raw import raw_to_table
 
         rdir = os.path.join(args.models, "rocket")
+        fdir = os.path.join(args.models, "filter")
+        # the samples are conditioned as at training time when main.py --filter saved its sections
+        flt = persist.load(fdir, device=dev) if os.path.isdir(fdir) else None
         rs = getattr(model, "raw_settings", None)
         if rs is not None:  # a DTW model: the windows' own samples, with the saved window settings
             raw = raw_to_table(args.raw, hz=rs["hz"], window_sec=rs["window_sec"], overlap=rs["overlap"], device=dev,
-                               samples=True)
+                               samples=True, filter=flt)
+        elif flt is not None and not os.path.isdir(rdir):  # the WISDM columns of the filtered stream
+            ws = flt.window_settings or {"hz": flt.hz, "window_sec": 10.0, "overlap": 0.0}
+            raw = raw_to_table(args.raw, hz=ws["hz"], window_sec=ws["window_sec"], overlap=ws["overlap"], device=dev,
+                               filter=flt)
         elif not os.path.isdir(rdir):
             raise FileNotFoundError(f"--raw needs the saved featurizer {rdir}: write it with "
                                     "main.py --raw PATH --rocket N --save-models DIR")
         else:
             rk = persist.load(rdir, device=dev)
             raw = raw_to_table(args.raw, hz=rk.hz, window_sec=rk.window / rk.hz, overlap=1.0 - rk.stride / rk.window,
-                               device=dev, rocket=rk)
+                               device=dev, rocket=rk, filter=flt)
     else:
         raw = read_csv(args.data, device=dev if (args.csv_device and dev.type == "cuda") else None)
     table = encode(pipe, raw, args.handle_invalid)
